@@ -7,9 +7,16 @@ weights/activations (f32 accumulation), batch of 8 synthetic 30 s 16 kHz chunks
 random-init weights never stop).  Weights are random-init from the shared seeded
 PRNG (no checkpoints offline).  One "step" = one batched call through the C ABI
 (spt_transcribe_batch, BASELINE.md:48's span): host PCM -> H2D -> log-mel -> encoder ->
-cross K/V -> 132 decoder passes -> tokens and text on the host.  `value` is that rate;
-`value_device_resident` is the same call on PCM already in HBM
-(spt_transcribe_batch_device).
+cross K/V -> 132 decoder passes -> tokens and text on the host.  `value` is that rate.
+
+A plain run sets up, warms up, times --steps such steps and prints the result line (`metric`,
+`value`, `ms_per_step`, phase times of the last step, ...).  --dump-outputs DIR also writes what the
+last timed step returned (tokens and the top-1 / top-2 log-probabilities per decode step of every
+utterance) as DIR/<name>.npy: the inputs and weights are seeded, so two builds can be compared
+output for output.  --full adds every other measurement to the line: `value_device_resident` (the
+same call on PCM already in HBM, spt_transcribe_batch_device), the per-kernel probe roofline, the
+app-call latencies, the CPU baselines, Whisper Turbo, Whisper-small f32, Parakeet-V3 and the
+resampler; the --no-* options leave single legs of it out.
 
 --gpus N (BASELINE.json configs[3]): one process per GPU.  Launched by torchrun (WORLD_SIZE
 set) each rank runs here; launched plainly, this process starts the N ranks itself
@@ -57,6 +64,11 @@ def parse():
     ap.add_argument("--model", default=MODEL_SPEC)
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--decode-steps", type=int, default=N_STEPS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: device-resident PCM, kernel probes, "
+                         "app latency, CPU baselines, Turbo, Whisper-small f32, Parakeet-V3, resampler")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-app-latency", action="store_true", help="skip the B=1 whisper_full (app default) latency")
     ap.add_argument("--no-probe", action="store_true", help="skip the per-kernel HIP-event probes")
@@ -68,7 +80,10 @@ def parse():
                     help="nccl (= RCCL) for the real run; gloo only to rehearse N > 1 ranks on one GPU")
     ap.add_argument("--no-weight-bcast", action="store_true",
                     help="N > 1: every rank loads the model itself instead of rank 0 + RCCL broadcast")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.parakeet_only and not args.full:
+        ap.error("--parakeet-only selects among the --full measurements: pass --full as well")
+    return args
 
 
 def _free_port() -> int:
@@ -557,6 +572,18 @@ def small_f32_bench(device: int, steps: int, warmup: int, decode_steps: int, wit
     return out
 
 
+def dump_outputs(out_dir: str, results, rank: int) -> None:
+    """What one batched call returned, as float arrays [batch][decode steps]: the tokens (ids are
+    exact in float64) and the top-1 / top-2 log-probabilities of every decode step.  Rank 0 writes
+    <name>.npy, rank r > 0 its own shard as <name>_rank<r>.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(out_dir, f"tokens{sfx}.npy"), np.array([r.tokens for r in results], dtype=np.float64))
+    np.save(os.path.join(out_dir, f"top1{sfx}.npy"), np.stack([np.asarray(r.top1, dtype=np.float32) for r in results]))
+    np.save(os.path.join(out_dir, f"top2{sfx}.npy"), np.stack([np.asarray(r.top2, dtype=np.float32) for r in results]))
+
+
 def main():
     args = parse()
     world_env = os.environ.get("WORLD_SIZE")
@@ -595,7 +622,7 @@ def main():
     lo, hi = shard_range(world * B, world, rank)
     pcm = np.stack([synth_audio(i) for i in range(lo, hi)])
     pcm_list = [pcm[i] for i in range(B)]
-    pcm_dev = torch.from_numpy(pcm).to(dev)
+    pcm_dev = torch.from_numpy(pcm).to(dev) if args.full else None
     torch.cuda.synchronize()
 
     # N > 1: rank 0 loads (generates / dequantises) the weights, one RCCL broadcast over xGMI
@@ -643,17 +670,20 @@ def main():
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0, device=dev)
         assert all(len(r.tokens) == args.decode_steps for r in res)
-        return dt, float(np.median(np.diff(marks))), eng.timings()
+        return dt, float(np.median(np.diff(marks))), eng.timings(), res
 
-    dt, med, phases = timed(step_host)
-    dt_dev, med_dev, phases_dev = timed(step_dev)
+    dt, med, phases, res = timed(step_host)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, rank)
+    if args.full:
+        dt_dev, med_dev, phases_dev, _ = timed(step_dev)
     rank_ms = [None] * world
     if world > 1:
         dist.all_gather_object(rank_ms, round(med * 1e3, 3))
     # the median step; the slowest rank's median (weak scaling: every rank's
     # step must finish), next to the mean over the barrier-bracketed region
     med_max = max_over_ranks(med, device=dev)
-    med_dev_max = max_over_ranks(med_dev, device=dev)
+    med_dev_max = max_over_ranks(med_dev, device=dev) if args.full else None
 
     audio_step = world * B * CHUNK_S
     value = audio_step / med_max
@@ -662,7 +692,7 @@ def main():
 
     roof = kernels = None
     cpu = app = None
-    if rank == 0:
+    if rank == 0 and args.full:
         if not args.no_probe:
             roof, kernels = roofline(eng)
         if world == 1 and not args.no_app_latency:
@@ -670,16 +700,16 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.model, args.decode_steps)
     rs = None
-    if rank == 0 and world == 1 and not args.no_parakeet:
+    if args.full and rank == 0 and world == 1 and not args.no_parakeet:
         rs = resampler_bench(local, not args.no_cpu_baseline)
     tb = None
-    if rank == 0 and world == 1 and not args.no_turbo and args.model == "synthetic:large-v3":
+    if args.full and rank == 0 and world == 1 and not args.no_turbo and args.model == "synthetic:large-v3":
         tb = turbo_bench(local, pcm_list, min(args.steps, 5), 1, args.decode_steps)
     c2 = None
-    if rank == 0 and world == 1 and not args.no_c2 and args.model == "synthetic:large-v3":
+    if args.full and rank == 0 and world == 1 and not args.no_c2 and args.model == "synthetic:large-v3":
         c2 = small_f32_bench(local, args.steps, args.warmup, args.decode_steps, not args.no_cpu_baseline)
     pk = None
-    if rank == 0 and world == 1 and not args.no_parakeet:
+    if args.full and rank == 0 and world == 1 and not args.no_parakeet:
         eng.unload_model()  # free the Whisper arenas first
         pk = parakeet_bench(local, min(args.steps, 10), max(1, args.warmup), not args.no_cpu_baseline)
     if rank == 0:
@@ -694,13 +724,16 @@ def main():
                                    f"{PROMPT_LEN}-token prompt + {args.decode_steps} decode steps, host PCM in, text out",
                        "model": args.model, "global_batch": world * B, "seq_len": 1500,
                        "decode_steps": args.decode_steps, "parallelism": f"replicas x{world} (utterance shards)"},
-            "value_device_resident": round(audio_step / med_dev_max, 3),
-            "ms_per_step_device_resident": round(med_dev_max * 1000.0, 3),
             "phases_ms": {k: round(v, 3) for k, v in phases.items() if k.endswith("_ms")},
-            "phases_ms_device_resident": {k: round(v, 3) for k, v in phases_dev.items() if k.endswith("_ms")},
-            "roofline": roof, "rooflines": phase_rooflines(info, phases, B, args.decode_steps, args.dtype),
-            "kernels": kernels, "cpu_baseline": cpu,
+            "rooflines": phase_rooflines(info, phases, B, args.decode_steps, args.dtype),
         }
+        if args.full:
+            out.update({
+                "value_device_resident": round(audio_step / med_dev_max, 3),
+                "ms_per_step_device_resident": round(med_dev_max * 1000.0, 3),
+                "phases_ms_device_resident": {k: round(v, 3) for k, v in phases_dev.items() if k.endswith("_ms")},
+                "roofline": roof, "kernels": kernels, "cpu_baseline": cpu,
+            })
         if app:
             out["app_call_latency_b1"] = app
         if world > 1:

@@ -1,5 +1,5 @@
-"""Agreement of bench.py's HIP-event kernel probes with rocprofv3: one bench run
-under rocprofv3 --kernel-trace (SPT_ENC_GROUPS=1, so each encoder kernel is one full-batch launch),
+"""Agreement of bench.py's HIP-event kernel probes with rocprofv3: one
+`bench.py --full` run under rocprofv3 --kernel-trace (SPT_ENC_GROUPS=1, so each encoder kernel is one full-batch launch),
 then for every probed kernel: the probe's average (the bench line's `kernels`), rocprofv3's average
 over the same launches, and rocprofv3's average over the timed calls' launches.  Each encoder probe
 runs encoder layer 0 `iters` times (every kernel of the layer, events around its own), fc1's probe
