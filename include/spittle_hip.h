@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SPT_ABI_VERSION 12
+#define SPT_ABI_VERSION 13
 
 typedef enum {
     SPT_OK = 0,
@@ -45,7 +45,10 @@ typedef enum {
     SPT_ERR_INTERNAL = 6
 } spt_status;
 
-typedef enum { SPT_DTYPE_F32 = 0, SPT_DTYPE_BF16 = 1, SPT_DTYPE_F16 = 2 /* Parakeet only */ } spt_dtype;
+typedef enum {
+    SPT_DTYPE_F32 = 0, SPT_DTYPE_BF16 = 1, SPT_DTYPE_F16 = 2 /* Parakeet only */,
+    SPT_DTYPE_I8 = 3 /* ABI 13, spt_pk_model_params.dtype only: the int8 ONNX export's arithmetic */
+} spt_dtype;
 
 /* decode flags (spt_infer_params.flags) */
 #define SPT_SUPPRESS_BLANK  1u  /* whisper_full_params.suppress_blank (default on) */
@@ -291,11 +294,19 @@ spt_status spt_debug_ggml_dequant(int32_t ggml_type, const void* src, int64_t n,
  * BASELINE config) or f32; the prediction network and joint always in f32.  Weights come from a
  * synthetic spec or tensor by tensor through spt_parakeet_set_tensor (the id table of
  * oracle/po_model.c, NeMo layouts; spittle_amd.parakeet.load_nemo maps a .nemo checkpoint).
+ *
+ * ABI 13: SPT_DTYPE_I8 runs the encoder as ONNX Runtime runs the app's quantize_dynamic export: the
+ * f32 engine, with every encoder Linear and pointwise convolution as DynamicQuantizeLinear (the
+ * input to uint8, one range per utterance) -> MatMulInteger / ConvInteger on int8 MFMAs (exact
+ * int32 accumulators) -> scale, bias, activation.  A model directory's integers, scales and zero
+ * points are used as stored; f32 weights of those layers (synthetic specs, set_tensor, QDQ
+ * directories) are quantised at load, symmetric per tensor.  The joint and the TDT decoder stay
+ * f32 on dequantised weights.  DESIGN.md §9.7 is the contract.
  * ============================================================================================== */
 typedef struct spt_pk_ctx spt_pk_ctx;
 
 typedef struct {
-    int32_t dtype;        /* SPT_DTYPE_F16 (default) or SPT_DTYPE_F32 (bf16 also accepted) */
+    int32_t dtype;        /* SPT_DTYPE_F16 (default), SPT_DTYPE_F32 or SPT_DTYPE_I8 (bf16 also accepted) */
     int32_t device;
     int32_t max_batch;    /* utterances (chunks) per device pass, <= 64 */
     float max_seconds;    /* workspace size: the longest utterance one pass takes before it grows.
@@ -367,6 +378,12 @@ typedef struct spt_pk_onnx spt_pk_onnx;
 spt_status spt_parakeet_onnx_open(const char* dir, spt_pk_onnx** out, spt_pk_model_info* info, char* err, size_t errlen);
 /* a tensor's f32 values (NeMo layout) by engine tensor id: its element count, or -1 */
 int64_t spt_parakeet_onnx_tensor(const spt_pk_onnx* h, int32_t tensor_id, const float** data);
+/* ABI 13: a weight consumed by MatMulInteger / ConvInteger exactly as the file stores it: the
+ * integers in the engine's [N][K] orientation (int8 or uint8 values, widened to int16), the scales
+ * and zero points and their count (1, or N: one per output channel).  Returns the element count, or
+ * -1 for a tensor no integer op consumes.  (q - zero_point) * scale is the f32 tensor above. */
+int64_t spt_parakeet_onnx_qtensor(const spt_pk_onnx* h, int32_t tensor_id, const int16_t** q, const float** scales,
+                                  const int32_t** zero_points, int32_t* n_scales);
 /* vocab.txt's piece for a token id (NULL past the vocabulary or without vocab.txt) */
 const char* spt_parakeet_onnx_piece(const spt_pk_onnx* h, int32_t token_id);
 void spt_parakeet_onnx_close(spt_pk_onnx* h);
@@ -417,6 +434,26 @@ spt_status spt_parakeet_debug_last_encoder(spt_pk_ctx* ctx, int32_t b, float* ou
 spt_status spt_parakeet_debug_decode(spt_pk_ctx* ctx, const float* enc, int32_t T3, int32_t max_symbols,
                                      spt_pk_result** out);
 spt_status spt_parakeet_debug_weight_checksum(spt_pk_ctx* ctx, int32_t tensor_id, double* out2);
+/* ABI 13 test hooks of the int8 mode.
+ * debug_qgemm: the three int8 kernels alone, without a model.  a [m][k] f32 rows in n_groups row
+ * groups (utterances: each its own quantisation range) of group_len rows; w [n][k] stored integers
+ * (int8 or uint8 values) with n_scales (1 or n) scales / zero points (NULL: zero); optional bias
+ * [n]; act an spt_pk_act.  Out: q [m][k] the uint8 quantised input, sa / za [n_groups], acc [m][n]
+ * the int32 accumulators, y [m][n].  k a multiple of 64 (<= 4096), n a multiple of 16.
+ * debug_tap: arm a capture, in the next spt_parakeet_debug_encode, of the quantised GEMM whose
+ * weight is tensor_id (5, 9, 11; per layer 1000 + 64 l + {2, 4, 8, 14, 16, 21, 29, 33, 35}; the
+ * stacked q / k / v GEMM is named by linear_q, + 8).  SPT_ERR_INVALID_ARG for any other id,
+ * SPT_ERR_UNSUPPORTED on an engine of another dtype.
+ * debug_tap_read: dims = {M, K, N, bias_included}; a [M][K] the GEMM's f32 input rows, y [M][N]
+ * its stored f32 output (bias_included 0: a residual product, whose bias the next LayerNorm adds).
+ * a / y may be NULL to read dims first; capacities in elements. */
+typedef enum { SPT_PK_ACT_NONE = 0, SPT_PK_ACT_RELU = 1, SPT_PK_ACT_SWISH = 2 } spt_pk_act;
+spt_status spt_parakeet_debug_qgemm(int32_t device, const float* a, int32_t m, int32_t k, const int32_t* group_len,
+                                    int32_t n_groups, const int16_t* w, int32_t n, const float* w_scales,
+                                    const int32_t* w_zero_points, int32_t n_scales, const float* bias, int32_t act,
+                                    uint8_t* q, float* sa, int32_t* za, int32_t* acc, float* y, char* err, size_t errlen);
+spt_status spt_parakeet_debug_tap(spt_pk_ctx* ctx, int32_t tensor_id);
+spt_status spt_parakeet_debug_tap_read(spt_pk_ctx* ctx, int32_t* dims, float* a, int64_t a_cap, float* y, int64_t y_cap);
 
 /* ================================================================================================
  * ABI 7: the capture-side resampler.

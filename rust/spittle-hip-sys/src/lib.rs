@@ -1,4 +1,4 @@
-//! Raw bindings to `include/spittle_hip.h` (ABI 12), the C boundary of the MI355X-native Whisper
+//! Raw bindings to `include/spittle_hip.h` (ABI 13), the C boundary of the MI355X-native Whisper
 //! and Parakeet-V3 backend.  One item per declaration of the header, same names, same layouts (x86-64 SysV; the
 //! layouts are checked field by field against gcc by tests/test_capi.py).  Safe wrappers live in
 //! the `spittle-hip` crate.
@@ -6,7 +6,7 @@
 
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const SPT_ABI_VERSION: c_int = 12;
+pub const SPT_ABI_VERSION: c_int = 13;
 pub const SPT_PK_STAGE_COUNT: c_int = 9;
 
 pub type spt_status = c_int;
@@ -22,6 +22,12 @@ pub type spt_dtype = c_int;
 pub const SPT_DTYPE_F32: spt_dtype = 0;
 pub const SPT_DTYPE_BF16: spt_dtype = 1;
 pub const SPT_DTYPE_F16: spt_dtype = 2;
+/// ABI 13, `spt_pk_model_params.dtype` only: the int8 ONNX export's own arithmetic
+pub const SPT_DTYPE_I8: spt_dtype = 3;
+/// `spt_pk_act` of `spt_parakeet_debug_qgemm`
+pub const SPT_PK_ACT_NONE: i32 = 0;
+pub const SPT_PK_ACT_RELU: i32 = 1;
+pub const SPT_PK_ACT_SWISH: i32 = 2;
 
 pub const SPT_SUPPRESS_BLANK: u32 = 1;
 pub const SPT_NO_TIMESTAMPS: u32 = 2;
@@ -308,6 +314,38 @@ extern "C" {
         out: *mut *mut spt_pk_result,
     ) -> spt_status;
     pub fn spt_parakeet_debug_weight_checksum(ctx: *mut spt_pk_ctx, tensor_id: i32, out2: *mut f64) -> spt_status;
+    // ---- ABI 13: test hooks of the int8 mode (SPT_DTYPE_I8)
+    pub fn spt_parakeet_debug_qgemm(
+        device: i32,
+        a: *const f32,
+        m: i32,
+        k: i32,
+        group_len: *const i32,
+        n_groups: i32,
+        w: *const i16,
+        n: i32,
+        w_scales: *const f32,
+        w_zero_points: *const i32,
+        n_scales: i32,
+        bias: *const f32,
+        act: i32,
+        q: *mut u8,
+        sa: *mut f32,
+        za: *mut i32,
+        acc: *mut i32,
+        y: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_parakeet_debug_tap(ctx: *mut spt_pk_ctx, tensor_id: i32) -> spt_status;
+    pub fn spt_parakeet_debug_tap_read(
+        ctx: *mut spt_pk_ctx,
+        dims: *mut i32,
+        a: *mut f32,
+        a_cap: i64,
+        y: *mut f32,
+        y_cap: i64,
+    ) -> spt_status;
 
     // ---- ABI 7: capture-side resampler (audio_toolkit/audio/resampler.rs FrameResampler)
     pub fn spt_resampler_create(
@@ -342,6 +380,15 @@ extern "C" {
         errlen: usize,
     ) -> spt_status;
     pub fn spt_parakeet_onnx_tensor(h: *const spt_pk_onnx, tensor_id: i32, data: *mut *const f32) -> i64;
+    // ABI 13: a MatMulInteger / ConvInteger weight as stored ([N][K] integers widened to i16)
+    pub fn spt_parakeet_onnx_qtensor(
+        h: *const spt_pk_onnx,
+        tensor_id: i32,
+        q: *mut *const i16,
+        scales: *mut *const f32,
+        zero_points: *mut *const i32,
+        n_scales: *mut i32,
+    ) -> i64;
     pub fn spt_parakeet_onnx_piece(h: *const spt_pk_onnx, token_id: i32) -> *const c_char;
     pub fn spt_parakeet_onnx_close(h: *mut spt_pk_onnx);
 

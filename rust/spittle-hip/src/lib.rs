@@ -1,5 +1,5 @@
 //! `HipWhisperEngine` and `HipParakeetEngine`: the `transcribe_rs::TranscriptionEngine` surfaces
-//! Spittle binds to, backed by the MI355X-native library (`libspittle_hip.so`, C ABI 12), plus `HipFrameResampler` and
+//! Spittle binds to, backed by the MI355X-native library (`libspittle_hip.so`, C ABI 13), plus `HipFrameResampler` and
 //! `HipSmoothedVad` (the capture-side resampler and voice-activity gate).
 //!
 //! What it replaces in the app (/root/reference/src-tauri/src/managers/transcription.rs):
@@ -311,9 +311,13 @@ impl Drop for HipWhisperReplicas {
 
 /// Device-side Parakeet parameters (`spt_pk_model_params`).  `int8()` mirrors the app's
 /// `ParakeetModelParams::int8()` (transcription.rs:281); the network runs with an fp16 encoder.
+/// `int8_exact()` runs the int8 export's own arithmetic instead (`SPT_DTYPE_I8`: every encoder
+/// Linear and pointwise convolution as DynamicQuantizeLinear -> MatMulInteger on the stored
+/// integers, the rest f32); it takes precedence over `fp16`.
 #[derive(Clone, Copy, Debug)]
 pub struct HipParakeetModelParams {
     pub fp16: bool,
+    pub int8_exact: bool,
     pub device: i32,
     pub max_batch: i32,
     pub max_seconds: f32,
@@ -321,7 +325,10 @@ pub struct HipParakeetModelParams {
 
 impl HipParakeetModelParams {
     pub fn int8() -> Self {
-        Self { fp16: true, device: 0, max_batch: 8, max_seconds: 30.0 }
+        Self { fp16: true, int8_exact: false, device: 0, max_batch: 8, max_seconds: 30.0 }
+    }
+    pub fn int8_exact() -> Self {
+        Self { fp16: false, int8_exact: true, device: 0, max_batch: 8, max_seconds: 30.0 }
     }
 }
 
@@ -390,7 +397,13 @@ impl TranscriptionEngine for HipParakeetEngine {
             sys::spt_parakeet_default_model_params(mp.as_mut_ptr());
             mp.assume_init()
         };
-        mp.dtype = if params.fp16 { sys::SPT_DTYPE_F16 } else { sys::SPT_DTYPE_F32 };
+        mp.dtype = if params.int8_exact {
+            sys::SPT_DTYPE_I8
+        } else if params.fp16 {
+            sys::SPT_DTYPE_F16
+        } else {
+            sys::SPT_DTYPE_F32
+        };
         mp.device = params.device;
         mp.max_batch = params.max_batch;
         mp.max_seconds = params.max_seconds;

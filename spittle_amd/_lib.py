@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(HERE, "libspittle_hip.so")
 # status codes
 SPT_OK, SPT_ERR_INVALID_ARG, SPT_ERR_LOAD, SPT_ERR_DEVICE, SPT_ERR_OOM, SPT_ERR_UNSUPPORTED, SPT_ERR_INTERNAL = range(7)
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "LOAD", 3: "DEVICE", 4: "OOM", 5: "UNSUPPORTED", 6: "INTERNAL"}
-SPT_DTYPE_F32, SPT_DTYPE_BF16, SPT_DTYPE_F16 = 0, 1, 2
+SPT_DTYPE_F32, SPT_DTYPE_BF16, SPT_DTYPE_F16, SPT_DTYPE_I8 = 0, 1, 2, 3
 SPT_SUPPRESS_BLANK, SPT_NO_TIMESTAMPS, SPT_IGNORE_EOT, SPT_SUPPRESS_NST = 1, 2, 4, 8
 
 # every symbol include/spittle_hip.h declares
@@ -42,6 +42,8 @@ EXPORTS = [
     "spt_vad_last_error", "spt_vad_destroy",
     # ABI 10: Parakeet encoder stage profile
     "spt_parakeet_profile_encoder",
+    # ABI 13: the Parakeet encoder's int8 mode (SPT_DTYPE_I8)
+    "spt_parakeet_onnx_qtensor", "spt_parakeet_debug_qgemm", "spt_parakeet_debug_tap", "spt_parakeet_debug_tap_read",
 ]
 SPT_PK_WEIGHTS_EMPTY = 1
 SPT_PK_TS_TOKEN, SPT_PK_TS_WORD, SPT_PK_TS_SEGMENT = 0, 1, 2
@@ -201,6 +203,9 @@ def load():
     L.spt_parakeet_onnx_open.argtypes = [C.c_char_p, C.POINTER(vp), C.POINTER(PkModelInfo), C.c_char_p, C.c_size_t]
     L.spt_parakeet_onnx_tensor.restype = C.c_int64
     L.spt_parakeet_onnx_tensor.argtypes = [vp, C.c_int32, C.POINTER(C.POINTER(C.c_float))]
+    L.spt_parakeet_onnx_qtensor.restype = C.c_int64
+    L.spt_parakeet_onnx_qtensor.argtypes = [vp, C.c_int32, C.POINTER(C.POINTER(C.c_int16)), C.POINTER(fp),
+                                            C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_int32)]
     L.spt_parakeet_onnx_piece.restype = C.c_char_p
     L.spt_parakeet_onnx_piece.argtypes = [vp, C.c_int32]
     L.spt_parakeet_onnx_close.argtypes = [vp]
@@ -224,6 +229,12 @@ def load():
     L.spt_parakeet_debug_decode.argtypes = [vp, fp, C.c_int32, C.c_int32, PR]
     L.spt_parakeet_debug_last_encoder.argtypes = [vp, C.c_int32, fp, C.POINTER(C.c_int32)]
     L.spt_parakeet_debug_weight_checksum.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+    i32p = C.POINTER(C.c_int32)
+    L.spt_parakeet_debug_qgemm.argtypes = [C.c_int32, fp, C.c_int32, C.c_int32, i32p, C.c_int32, C.POINTER(C.c_int16),
+                                           C.c_int32, fp, i32p, C.c_int32, fp, C.c_int32, C.POINTER(C.c_uint8), fp, i32p,
+                                           i32p, fp, C.c_char_p, C.c_size_t]
+    L.spt_parakeet_debug_tap.argtypes = [vp, C.c_int32]
+    L.spt_parakeet_debug_tap_read.argtypes = [vp, i32p, fp, C.c_int64, fp, C.c_int64]
     L.spt_resampler_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp), C.c_char_p,
                                        C.c_size_t]
     L.spt_resampler_create.restype = C.c_int
@@ -256,7 +267,7 @@ def load():
                                                           "spt_parakeet_default_infer_params", "spt_parakeet_destroy",
                                                           "spt_parakeet_last_error", "spt_parakeet_result_free",
                                                           "spt_parakeet_onnx_tensor", "spt_parakeet_onnx_piece",
-                                                          "spt_parakeet_onnx_close"):
+                                                          "spt_parakeet_onnx_close", "spt_parakeet_onnx_qtensor"):
             getattr(L, fn).restype = C.c_int
     for fn in ("spt_weights_arena", "spt_weights_commit", "spt_ctx_create_replicas", "spt_transcribe_batch_replicas",
                "spt_weights_export", "spt_weights_import", "spt_ctx_info", "spt_transcribe", "spt_transcribe_batch", "spt_transcribe_batch_device",

@@ -1,4 +1,4 @@
-// capi_pk.cpp -- the spt_parakeet_* half of include/spittle_hip.h (ABI 6).
+// capi_pk.cpp -- the spt_parakeet_* half of include/spittle_hip.h (ABI 6; the int8 mode: ABI 13).
 //
 // Mirrors transcribe-rs' ParakeetEngine as Spittle drives it (/root/reference/src-tauri/src/
 // managers/transcription.rs: load_model_with_params 278-297, transcribe_samples with
@@ -49,6 +49,7 @@ spt_status fail(spt_pk_ctx* c, spt_status s, const std::string& m) {
 spt_status classify(const std::exception& e) {
     if (dynamic_cast<const spt::HipError*>(&e)) return SPT_ERR_DEVICE;
     if (dynamic_cast<const std::bad_alloc*>(&e)) return SPT_ERR_OOM;
+    if (dynamic_cast<const spt::PkUnsupported*>(&e)) return SPT_ERR_UNSUPPORTED;
     if (std::string(e.what()).find("out of device memory") != std::string::npos) return SPT_ERR_OOM;
     return SPT_ERR_INVALID_ARG;
 }
@@ -203,7 +204,7 @@ spt_status spt_parakeet_create(const char* model_spec, const spt_pk_model_params
     spt_pk_model_params mp;
     spt_parakeet_default_model_params(&mp);
     if (params) mp = *params;
-    if (mp.dtype != SPT_DTYPE_F32 && mp.dtype != SPT_DTYPE_F16 && mp.dtype != SPT_DTYPE_BF16) {
+    if (mp.dtype != SPT_DTYPE_F32 && mp.dtype != SPT_DTYPE_F16 && mp.dtype != SPT_DTYPE_BF16 && mp.dtype != SPT_DTYPE_I8) {
         set_err(err, errlen, "bad dtype");
         return SPT_ERR_INVALID_ARG;
     }
@@ -263,7 +264,8 @@ spt_status spt_parakeet_create(const char* model_spec, const spt_pk_model_params
     spt_pk_ctx* c = new (std::nothrow) spt_pk_ctx();
     if (!c) return SPT_ERR_OOM;
     try {
-        const int dt = mp.dtype == SPT_DTYPE_F16 ? spt::DT_F16 : mp.dtype == SPT_DTYPE_BF16 ? spt::DT_BF16 : spt::DT_F32;
+        const int dt = mp.dtype == SPT_DTYPE_F16 ? spt::DT_F16 : mp.dtype == SPT_DTYPE_BF16 ? spt::DT_BF16
+                       : mp.dtype == SPT_DTYPE_I8 ? spt::DT_I8 : spt::DT_F32;
         c->eng.reset(new spt::ParakeetEngine(dm, dt, mp.device, mp.max_batch, max_samples, seed,
                                              !(mp.flags & SPT_PK_WEIGHTS_EMPTY)));
         if (onnx) {
@@ -271,7 +273,13 @@ spt_status spt_parakeet_create(const char* model_spec, const spt_pk_model_params
                 if (!onnx->tensors.count(tid))
                     throw std::runtime_error(std::string(model_spec) + ": no tensor for " + spt::pk_tensor_name(tid));
             for (auto& kv : onnx->tensors) {  // host copies freed as they land
-                c->eng->set_tensor(kv.first, kv.second.data(), (int64_t)kv.second.size());
+                // int8 mode: a quantised layer takes the integers the file stores, not requantised ones
+                auto q = onnx->qtensors.find(kv.first);
+                if (q != onnx->qtensors.end() && c->eng->is_q_weight(kv.first))
+                    c->eng->set_tensor_q(kv.first, q->second.q.data(), (int64_t)q->second.q.size(), q->second.scales.data(),
+                                         q->second.zero_points.data(), (int)q->second.scales.size());
+                else
+                    c->eng->set_tensor(kv.first, kv.second.data(), (int64_t)kv.second.size());
                 std::vector<float>().swap(kv.second);
             }
             c->pieces = onnx->pieces;
@@ -332,6 +340,18 @@ int64_t spt_parakeet_onnx_tensor(const spt_pk_onnx* h, int32_t tensor_id, const 
     return (int64_t)it->second.size();
 }
 
+int64_t spt_parakeet_onnx_qtensor(const spt_pk_onnx* h, int32_t tensor_id, const int16_t** q, const float** scales,
+                                  const int32_t** zero_points, int32_t* n_scales) {
+    if (!h || !q || !scales || !zero_points || !n_scales) return -1;
+    auto it = h->m.qtensors.find(tensor_id);
+    if (it == h->m.qtensors.end()) return -1;
+    *q = it->second.q.data();
+    *scales = it->second.scales.data();
+    *zero_points = it->second.zero_points.data();
+    *n_scales = (int32_t)it->second.scales.size();
+    return (int64_t)it->second.q.size();
+}
+
 const char* spt_parakeet_onnx_piece(const spt_pk_onnx* h, int32_t token_id) {
     if (!h || token_id < 0 || (size_t)token_id >= h->m.pieces.size()) return nullptr;
     return h->m.pieces[token_id].c_str();
@@ -348,7 +368,8 @@ spt_status spt_parakeet_info(const spt_pk_ctx* ctx, spt_pk_model_info* info) {
     info->sub_ch = d.sub_ch; info->conv_k = d.conv_k; info->pred = d.pred; info->n_vocab = d.n_vocab;
     info->n_dur = d.n_dur;
     const int dt = ctx->eng->dtype();
-    info->dtype = dt == spt::DT_F16 ? SPT_DTYPE_F16 : dt == spt::DT_BF16 ? SPT_DTYPE_BF16 : SPT_DTYPE_F32;
+    info->dtype = dt == spt::DT_F16 ? SPT_DTYPE_F16 : dt == spt::DT_BF16 ? SPT_DTYPE_BF16
+                  : dt == spt::DT_I8 ? SPT_DTYPE_I8 : SPT_DTYPE_F32;
     info->max_batch = ctx->eng->max_batch();
     info->max_samples = ctx->eng->max_samples();
     info->reserved0 = 0;
@@ -570,12 +591,63 @@ spt_status spt_parakeet_debug_decode(spt_pk_ctx* ctx, const float* enc, int32_t 
     }
 }
 
+spt_status spt_parakeet_debug_qgemm(int32_t device, const float* a, int32_t m, int32_t k, const int32_t* group_len,
+                                    int32_t n_groups, const int16_t* w, int32_t n, const float* w_scales,
+                                    const int32_t* w_zero_points, int32_t n_scales, const float* bias, int32_t act,
+                                    uint8_t* q, float* sa, int32_t* za, int32_t* acc, float* y, char* err, size_t errlen) {
+    if (!a || !group_len || !w || !w_scales || !q || !sa || !za || !acc || !y) {
+        set_err(err, errlen, "null argument");
+        return SPT_ERR_INVALID_ARG;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        set_err(err, errlen, "no HIP device available");
+        return SPT_ERR_DEVICE;
+    }
+    if (device < 0 || device >= ndev) {
+        set_err(err, errlen, "device ordinal out of range");
+        return SPT_ERR_INVALID_ARG;
+    }
+    try {
+        spt::pk_i8_debug_gemm(device, a, m, k, group_len, n_groups, w, n, w_scales, w_zero_points, n_scales, bias, act, q,
+                              sa, za, acc, y);
+        return SPT_OK;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return classify(e);
+    }
+}
+
+spt_status spt_parakeet_debug_tap(spt_pk_ctx* ctx, int32_t tensor_id) {
+    if (!ctx) return SPT_ERR_INVALID_ARG;
+    if (ctx->eng->dtype() != spt::DT_I8) return fail(ctx, SPT_ERR_UNSUPPORTED, "taps exist in the int8 mode only");
+    if (!ctx->eng->debug_tap(tensor_id)) return fail(ctx, SPT_ERR_INVALID_ARG, "tensor id names no quantised GEMM");
+    return SPT_OK;
+}
+
+spt_status spt_parakeet_debug_tap_read(spt_pk_ctx* ctx, int32_t* dims, float* a, int64_t a_cap, float* y, int64_t y_cap) {
+    if (!ctx || !dims) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
+    if (ctx->eng->dtype() != spt::DT_I8) return fail(ctx, SPT_ERR_UNSUPPORTED, "taps exist in the int8 mode only");
+    const spt::ParakeetEngine::Tap& t = ctx->eng->tap();
+    if (!t.done) return fail(ctx, SPT_ERR_INVALID_ARG, "no capture: arm a tap, then run spt_parakeet_debug_encode");
+    dims[0] = t.M; dims[1] = t.K; dims[2] = t.N; dims[3] = t.bias_included;
+    if (a) {
+        if (a_cap < (int64_t)t.a.size()) return fail(ctx, SPT_ERR_INVALID_ARG, "input buffer too small");
+        memcpy(a, t.a.data(), t.a.size() * 4);
+    }
+    if (y) {
+        if (y_cap < (int64_t)t.y.size()) return fail(ctx, SPT_ERR_INVALID_ARG, "output buffer too small");
+        memcpy(y, t.y.data(), t.y.size() * 4);
+    }
+    return SPT_OK;
+}
+
 spt_status spt_parakeet_debug_weight_checksum(spt_pk_ctx* ctx, int32_t tensor_id, double* out2) {
     if (!ctx || !out2) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
     try {
         if (!ctx->eng->has_tensor(tensor_id)) return fail(ctx, SPT_ERR_INVALID_ARG, "unknown tensor id");
         if (!ctx->eng->debug_weight_checksum(tensor_id, out2))
-            return fail(ctx, SPT_ERR_UNSUPPORTED, "tensor is stored transposed inside a shared block");
+            return fail(ctx, SPT_ERR_UNSUPPORTED, "tensor is stored transposed inside a shared block, or as integers (int8 mode)");
         return SPT_OK;
     } catch (const std::exception& e) {
         return fail(ctx, classify(e), e.what());

@@ -199,7 +199,7 @@ template <typename T>
 __global__ __launch_bounds__(64) void rel_attn_kernel(const T* __restrict__ qkv, const T* __restrict__ p, int ldp,
                                                       const float* __restrict__ pu, const float* __restrict__ pv,
                                                       const int* __restrict__ lens, int Tp, int H, int dk,
-                                                      T* __restrict__ out) {
+                                                      T* __restrict__ out, int64_t p_bstride) {
     extern __shared__ float sm[];  // qu[dk] | qv[dk] | scores[Tp]
     float* qu = sm;
     float* qv = sm + dk;
@@ -213,6 +213,7 @@ __global__ __launch_bounds__(64) void rel_attn_kernel(const T* __restrict__ qkv,
         return;
     }
     const T* base = qkv + (size_t)b * Tp * 3 * d;
+    p += (size_t)b * p_bstride;  // the int8 mode's per-utterance projected positions (else 0)
     for (int e = lane; e < dk; e += 64) {
         const float q = to_f<T>(base[(size_t)i * 3 * d + h * dk + e]);
         qu[e] = q + pu[h * dk + e];
@@ -883,8 +884,9 @@ void pk_relpos(int dtype, int Tp, int d, void* pe, hipStream_t st) {
 }
 
 void pk_rel_attn(int dtype, const void* qkv, const void* p, int ldp, const float* pu, const float* pv, const int* lens,
-                 int B, int Tp, int H, int dk, void* out, hipStream_t st) {
+                 int B, int Tp, int H, int dk, void* out, hipStream_t st, int64_t p_bstride) {
     if (dk % 8 || dk > 256) throw std::runtime_error("pk_rel_attn: head dim must be a multiple of 8, <= 256");
+    if (p_bstride && dtype != DT_F32) throw std::runtime_error("pk_rel_attn: per-utterance positions are f32 only");
     const size_t smem = (size_t)(2 * dk + Tp) * 4;
     if (smem > 64 * 1024) throw std::runtime_error("pk_rel_attn: too many frames for the LDS score row");
     static const bool valu = getenv("SPT_PK_ATTN_VALU") != nullptr;  // A/B switch
@@ -902,13 +904,13 @@ void pk_rel_attn(int dtype, const void* qkv, const void* p, int ldp, const float
     dim3 grid(Tp, H, B);
     if (dtype == DT_F16)
         hipLaunchKernelGGL(rel_attn_kernel<f16>, grid, dim3(64), smem, st, (const f16*)qkv, (const f16*)p, ldp, pu, pv,
-                           lens, Tp, H, dk, (f16*)out);
+                           lens, Tp, H, dk, (f16*)out, (int64_t)0);
     else if (dtype == DT_BF16)
         hipLaunchKernelGGL(rel_attn_kernel<bf16>, grid, dim3(64), smem, st, (const bf16*)qkv, (const bf16*)p, ldp, pu, pv,
-                           lens, Tp, H, dk, (bf16*)out);
+                           lens, Tp, H, dk, (bf16*)out, (int64_t)0);
     else
         hipLaunchKernelGGL(rel_attn_kernel<float>, grid, dim3(64), smem, st, (const float*)qkv, (const float*)p, ldp, pu,
-                           pv, lens, Tp, H, dk, (float*)out);
+                           pv, lens, Tp, H, dk, (float*)out, p_bstride);
     SPT_LAUNCH_CHECK();
 }
 

@@ -7,7 +7,9 @@
 
 namespace spt {
 
-enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2 };  // DT_F16: the Parakeet encoder only
+// DT_F16: the Parakeet encoder only; DT_I8: the Parakeet encoder's int8 mode (f32 activations,
+// int8 GEMM operands: k_pk_i8.hip), no kernel outside it takes it
+enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3 };
 
 // ------------------------------------------------------------------ GEMM (k_gemm.hip)
 // Cross-attention K/V cache layout: per decoder layer [ceil(T/32)][B][H][2][32][64] -- 32-key

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "pk_onnx.h"
 
 namespace spt {
 
@@ -117,7 +118,17 @@ ParakeetEngine::ParakeetEngine(const PkDims& dm, int dtype, int device, int max_
     if (dm_.d % dm_.n_heads || (dm_.d / dm_.n_heads) % 8) throw std::runtime_error("head dim must be a multiple of 8");
     if (dm_.pred % 128 || dm_.d % 256 || dm_.ff % 256 || dm_.sub_ch % 128)
         throw std::runtime_error("Parakeet dims must be multiples of the GEMM tiles (pred % 128, d % 256, ff % 256, sub_ch % 128)");
-    esz_ = dtype == DT_F32 ? 4 : 2;
+    if (dtype == DT_I8) {  // every quantised GEMM's K: a multiple of the int8 MFMA's 64
+        const std::pair<int, int> ks[] = {{5, dm_.sub_ch}, {11, dm_.sub_ch * halve(halve(halve(dm_.n_mels)))},
+                                          {1002, dm_.d}, {1004, dm_.ff}};
+        for (auto& k : ks)
+            if (k.second % 64 || k.second > 4096)
+                throw PkUnsupported("int8 mode: " + pk_tensor_name(k.first) + " has K = " + std::to_string(k.second) +
+                                    ", not a multiple of 64 up to 4096");
+    }
+    adt_ = dtype == DT_I8 ? DT_F32 : dtype;
+    esz_ = adt_ == DT_F32 ? 4 : 2;
+    wesz_ = dtype == DT_I8 ? 1 : esz_;
     F1_ = halve(dm_.n_mels);
     F2_ = halve(F1_);
     F3_ = halve(F2_);
@@ -198,7 +209,24 @@ void ParakeetEngine::alloc_weights() {
         Carve c{warena_};
         specs_.clear();
         auto F32 = [&](int64_t n) { return (float*)c.take(n * 4); };
-        auto TT = [&](int64_t n) { return c.take(n * esz_); };
+        auto TT = [&](int64_t n) { return c.take(n * wesz_); };
+        if (!pass) qblk_.clear();
+        // int8 mode: a GEMM's weight block [N][K] with its per-column scales, zero points and sums
+        auto TQ = [&](int N, int Kq) {
+            void* w = TT((int64_t)N * Kq);
+            if (dt_ == DT_I8) {
+                QBlock q{};
+                q.sw = (float*)c.take((int64_t)N * 4);
+                q.zw = (int*)c.take((int64_t)N * 4);
+                q.cs = (int*)c.take((int64_t)N * 4);
+                q.N = N; q.K = Kq;
+                if (pass) qblk_[w] = q;
+            }
+            return w;
+        };
+        auto tap = [&](void* w, int tid, int col0, int n) {
+            if (pass && dt_ == DT_I8) qblk_[w].taps.push_back(QTap{tid, col0, n});
+        };
         auto add = [&](int tid, int64_t n, int kind, int exp, int mode, int dt, void* dst, int N = 1, int Kd = 0,
                        int ld = 0, int row0 = 0) {
             specs_.push_back(TSpec{tid, n, kind, exp, mode, dt, dst, N, Kd ? Kd : (int)n, ld, row0});
@@ -208,47 +236,50 @@ void ParakeetEngine::alloc_weights() {
             add(tid, n, kind, exp, PK_PLACE_COPY, DT_F32, p);
             return p;
         };
-        auto mat = [&](int tid, int64_t n, int fan, void* dst) { add(tid, n, PLAIN, fanin_exp(fan), PK_PLACE_COPY, dt_, dst); };
+        // a GEMM weight [N][fan] (its K is the fan-in)
+        auto mat = [&](int tid, int64_t n, int fan, void* dst) {
+            add(tid, n, PLAIN, fanin_exp(fan), PK_PLACE_COPY, dt_, dst, (int)(n / fan), fan);
+        };
         c0_w_ = f32t(1, (int64_t)C * 9, PLAIN, fanin_exp(9));
         c0_b_ = f32t(2, C, PLAIN, -5);
         dw1_w_ = f32t(3, (int64_t)C * 9, PLAIN, fanin_exp(9));
         dw1_b_ = f32t(4, C, PLAIN, -5);
-        pw1_w_ = TT((int64_t)C * C); mat(5, (int64_t)C * C, C, pw1_w_);
+        pw1_w_ = TQ(C, C); mat(5, (int64_t)C * C, C, pw1_w_); tap(pw1_w_, 5, 0, C);
         pw1_b_ = f32t(6, C, PLAIN, -5);
         dw2_w_ = f32t(7, (int64_t)C * 9, PLAIN, fanin_exp(9));
         dw2_b_ = f32t(8, C, PLAIN, -5);
-        pw2_w_ = TT((int64_t)C * C); mat(9, (int64_t)C * C, C, pw2_w_);
+        pw2_w_ = TQ(C, C); mat(9, (int64_t)C * C, C, pw2_w_); tap(pw2_w_, 9, 0, C);
         pw2_b_ = f32t(10, C, PLAIN, -5);
-        sub_w_ = TT((int64_t)d * C * F3_);
+        sub_w_ = TQ(d, C * F3_); tap(sub_w_, 11, 0, d);
         add(11, (int64_t)d * C * F3_, PLAIN, fanin_exp(C * F3_), PK_PLACE_SUBPERM, dt_, sub_w_, d, C * F3_, C, F3_);
         sub_b_ = f32t(12, d, PLAIN, -5);
-        pos_w_ = TT((int64_t)Ln * dd);
+        pos_w_ = TQ(Ln * d, d);
         L_.assign(Ln, Layer{});
         for (int l = 0; l < Ln; ++l) {
             Layer& y = L_[l];
             const int b = 1000 + 64 * l;
             y.ln1_w = f32t(b + 0, d, PLUS1, -3);
             y.ln1_b = f32t(b + 1, d, PLAIN, -4);
-            y.ff1_w1 = TT((int64_t)ff * d); mat(b + 2, (int64_t)ff * d, d, y.ff1_w1);
+            y.ff1_w1 = TQ(ff, d); mat(b + 2, (int64_t)ff * d, d, y.ff1_w1); tap(y.ff1_w1, b + 2, 0, ff);
             y.ff1_b1 = f32t(b + 3, ff, PLAIN, -5);
-            y.ff1_w2 = TT((int64_t)ff * d); mat(b + 4, (int64_t)ff * d, ff, y.ff1_w2);
+            y.ff1_w2 = TQ(d, ff); mat(b + 4, (int64_t)ff * d, ff, y.ff1_w2); tap(y.ff1_w2, b + 4, 0, d);
             y.ff1_b2 = f32t(b + 5, d, PLAIN, -5);
             y.lna_w = f32t(b + 6, d, PLUS1, -3);
             y.lna_b = f32t(b + 7, d, PLAIN, -4);
-            y.qkv_w = TT(3 * dd);
+            y.qkv_w = TQ(3 * d, d); tap(y.qkv_w, b + 8, 0, 3 * d);  // the stacked GEMM is named by linear_q
             y.qkv_b = F32(3 * d);
             for (int q = 0; q < 3; ++q) {
-                mat(b + 8 + 2 * q, dd, d, (char*)y.qkv_w + q * dd * esz_);
+                mat(b + 8 + 2 * q, dd, d, (char*)y.qkv_w + q * dd * wesz_);
                 add(b + 9 + 2 * q, d, PLAIN, -5, PK_PLACE_COPY, DT_F32, y.qkv_b + q * d);
             }
-            y.o_w = TT(dd); mat(b + 14, dd, d, y.o_w);
+            y.o_w = TQ(d, d); mat(b + 14, dd, d, y.o_w); tap(y.o_w, b + 14, 0, d);
             y.o_b = f32t(b + 15, d, PLAIN, -5);
-            mat(b + 16, dd, d, (char*)pos_w_ + l * dd * esz_);
+            mat(b + 16, dd, d, (char*)pos_w_ + l * dd * wesz_); tap(pos_w_, b + 16, l * d, d);
             y.pos_u = f32t(b + 17, d, PLAIN, -4);
             y.pos_v = f32t(b + 18, d, PLAIN, -4);
             y.lnc_w = f32t(b + 19, d, PLUS1, -3);
             y.lnc_b = f32t(b + 20, d, PLAIN, -4);
-            y.pw1_w = TT(2 * dd); mat(b + 21, 2 * dd, d, y.pw1_w);
+            y.pw1_w = TQ(2 * d, d); mat(b + 21, 2 * dd, d, y.pw1_w); tap(y.pw1_w, b + 21, 0, 2 * d);
             y.pw1_b = f32t(b + 22, 2 * d, PLAIN, -5);
             y.dw_w = f32t(b + 23, (int64_t)d * K, PLAIN, fanin_exp(K));
             y.dw_b = f32t(b + 24, d, PLAIN, -5);
@@ -256,13 +287,13 @@ void ParakeetEngine::alloc_weights() {
             y.bn_b = f32t(b + 26, d, PLAIN, -4);
             y.bn_m = f32t(b + 27, d, PLAIN, -4);
             y.bn_v = f32t(b + 28, d, PLUS1, -2);
-            y.pw2_w = TT(dd); mat(b + 29, dd, d, y.pw2_w);
+            y.pw2_w = TQ(d, d); mat(b + 29, dd, d, y.pw2_w); tap(y.pw2_w, b + 29, 0, d);
             y.pw2_b = f32t(b + 30, d, PLAIN, -5);
             y.ln2_w = f32t(b + 31, d, PLUS1, -3);
             y.ln2_b = f32t(b + 32, d, PLAIN, -4);
-            y.ff2_w1 = TT((int64_t)ff * d); mat(b + 33, (int64_t)ff * d, d, y.ff2_w1);
+            y.ff2_w1 = TQ(ff, d); mat(b + 33, (int64_t)ff * d, d, y.ff2_w1); tap(y.ff2_w1, b + 33, 0, ff);
             y.ff2_b1 = f32t(b + 34, ff, PLAIN, -5);
-            y.ff2_w2 = TT((int64_t)ff * d); mat(b + 35, (int64_t)ff * d, ff, y.ff2_w2);
+            y.ff2_w2 = TQ(d, ff); mat(b + 35, (int64_t)ff * d, ff, y.ff2_w2); tap(y.ff2_w2, b + 35, 0, d);
             y.ff2_b2 = f32t(b + 36, d, PLAIN, -5);
             y.lno_w = f32t(b + 37, d, PLUS1, -3);
             y.lno_b = f32t(b + 38, d, PLAIN, -4);
@@ -309,7 +340,170 @@ void ParakeetEngine::alloc_weights() {
     }
 }
 
+// ---- int8 mode: weights, all on the host at load time
+void pk_i8_prepare_weight(const int16_t* q, int N, int K, const float* scales, const int32_t* zps, int n_scales,
+                          PkQHost* o) {
+    if (n_scales != 1 && n_scales != N) throw std::runtime_error("int8 weight: one scale, or one per output channel");
+    const int64_t n = (int64_t)N * K;
+    int lo = 0, hi = 0;
+    for (int64_t i = 0; i < n; ++i) { lo = std::min<int>(lo, q[i]); hi = std::max<int>(hi, q[i]); }
+    // the MFMA operands are signed: uint8 weights are stored as w - 128, their zero points likewise
+    const int shift = hi > 127 ? 128 : 0;
+    if (hi - shift > 127 || lo - shift < -128) throw std::runtime_error("int8 weight: values outside one 8-bit range");
+    o->w.resize((size_t)n);
+    o->sw.resize(N); o->zw.resize(N); o->cs.resize(N);
+    for (int r = 0; r < N; ++r) {
+        int sum = 0;
+        for (int k = 0; k < K; ++k) {
+            const int v = q[(size_t)r * K + k] - shift;
+            o->w[(size_t)r * K + k] = (int8_t)v;
+            sum += v;
+        }
+        o->cs[r] = sum;
+        o->sw[r] = scales[n_scales == 1 ? 0 : r];
+        o->zw[r] = (zps ? zps[n_scales == 1 ? 0 : r] : 0) - shift;
+    }
+}
+
+// an f32 weight of a quantised layer: symmetric, per tensor (tests/onnx_parakeet.quantize "int8")
+void pk_i8_quantize_weight(const float* w, int64_t n, std::vector<int16_t>* q, float* scale) {
+    float amax = 0.0f;
+    for (int64_t i = 0; i < n; ++i) amax = std::max(amax, fabsf(w[i]));
+    const float s = (float)(std::max((double)amax, 1e-12) / 127.0);
+    q->resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        (*q)[(size_t)i] = (int16_t)std::min(127.0f, std::max(-127.0f, nearbyintf(w[i] / s)));
+    *scale = s;
+}
+
+void pk_i8_debug_gemm(int device, const float* A, int M, int K, const int* group_len, int n_groups, const int16_t* W,
+                      int N, const float* scales, const int32_t* zps, int n_scales, const float* bias, int act,
+                      uint8_t* q_out, float* sa_out, int32_t* za_out, int32_t* acc_out, float* y_out) {
+    if (M < 1 || n_groups < 1 || n_groups > 64 || K < 64 || K % 64 || K > 4096 || N < 16 || N % 16)
+        throw std::runtime_error("debug_qgemm: need M >= 1, 1..64 groups, K % 64 == 0 (<= 4096), N % 16 == 0");
+    if (act < PK_I8_NONE || act > PK_I8_SWISH) throw std::runtime_error("debug_qgemm: unknown activation");
+    int rows = 0, tot = 0;
+    for (int g = 0; g < n_groups; ++g) {
+        if (group_len[g] < 1) throw std::runtime_error("debug_qgemm: empty row group");
+        rows = std::max(rows, group_len[g]);
+        tot += group_len[g];
+    }
+    if (tot != M) throw std::runtime_error("debug_qgemm: the row groups do not add up to M");
+    PkQHost h;
+    pk_i8_prepare_weight(W, N, K, scales, zps, n_scales, &h);
+    // the engine's layout: every group padded to the longest one's rows
+    const int Mp = n_groups * rows;
+    std::vector<float> Ap((size_t)Mp * K, 0.0f);
+    for (int g = 0, m = 0; g < n_groups; m += group_len[g++])
+        memcpy(&Ap[(size_t)g * rows * K], A + (size_t)m * K, (size_t)group_len[g] * K * 4);
+    HIP_CHECK(hipSetDevice(device));
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() { if (p) (void)hipFree(p); }
+        void* get(size_t n) { HIP_CHECK(hipMalloc(&p, n)); return p; }
+    } bA, bQ, bR, bK, bS, bZ, bL, bW, bSw, bZw, bCs, bB, bC, bAcc;
+    float* dA = (float*)bA.get(Ap.size() * 4);
+    int8_t* dQ = (int8_t*)bQ.get((size_t)Mp * K);
+    int* dR = (int*)bR.get((size_t)Mp * 4);
+    unsigned* dK = (unsigned*)bK.get((size_t)n_groups * 8);
+    float* dS = (float*)bS.get((size_t)n_groups * 4);
+    int* dZ = (int*)bZ.get((size_t)n_groups * 4);
+    int* dL = (int*)bL.get((size_t)n_groups * 4);
+    int8_t* dW = (int8_t*)bW.get((size_t)N * K);
+    float* dSw = (float*)bSw.get((size_t)N * 4);
+    int* dZw = (int*)bZw.get((size_t)N * 4);
+    int* dCs = (int*)bCs.get((size_t)N * 4);
+    float* dB = bias ? (float*)bB.get((size_t)N * 4) : nullptr;
+    float* dC = (float*)bC.get((size_t)Mp * N * 4);
+    int* dAcc = (int*)bAcc.get((size_t)Mp * N * 4);
+    HIP_CHECK(hipMemcpy(dA, Ap.data(), Ap.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dL, group_len, (size_t)n_groups * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dW, h.w.data(), (size_t)N * K, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dSw, h.sw.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dZw, h.zw.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dCs, h.cs.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    if (bias) HIP_CHECK(hipMemcpy(dB, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemsetD32(dK, (int)0x80000000u, (size_t)n_groups * 2));
+    const PkI8Groups G{PK_I8_ROWS, rows, 1, dL, 1, 0};
+    pk_i8_minmax(dA, K, G, n_groups, dK, nullptr);
+    pk_i8_quantize(dA, K, G, n_groups, dK, dQ, dR, dS, dZ, nullptr);
+    PkI8Gemm g{};
+    g.Q = dQ; g.rowsum = dR; g.sa = dS; g.za = dZ; g.rows = rows;
+    g.W = dW; g.sw = dSw; g.zw = dZw; g.cs = dCs;
+    g.M = Mp; g.N = N; g.K = K; g.bias = dB; g.act = act; g.alpha = 1.0f;
+    g.C = dC; g.ldc = N; g.acc_out = dAcc;
+    pk_i8_gemm(g, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    std::vector<int8_t> Q((size_t)Mp * K);
+    std::vector<int32_t> acc((size_t)Mp * N);
+    std::vector<float> y((size_t)Mp * N);
+    HIP_CHECK(hipMemcpy(Q.data(), dQ, Q.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(acc.data(), dAcc, acc.size() * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(y.data(), dC, y.size() * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(sa_out, dS, (size_t)n_groups * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(za_out, dZ, (size_t)n_groups * 4, hipMemcpyDeviceToHost));
+    for (int g2 = 0, m = 0; g2 < n_groups; m += group_len[g2++])
+        for (int r = 0; r < group_len[g2]; ++r) {
+            const size_t src = (size_t)g2 * rows + r, dst = (size_t)m + r;
+            for (int k = 0; k < K; ++k) q_out[dst * K + k] = (uint8_t)(Q[src * K + k] + 128);
+            memcpy(acc_out + dst * N, &acc[src * N], (size_t)N * 4);
+            memcpy(y_out + dst * N, &y[src * N], (size_t)N * 4);
+        }
+}
+
+void ParakeetEngine::place_q(const TSpec& t, const int16_t* q, const float* scales, const int32_t* zps, int n_scales) {
+    auto it = qblk_.upper_bound(t.dst);
+    if (it == qblk_.begin()) throw std::runtime_error("internal: no int8 block for tensor " + std::to_string(t.tid));
+    --it;
+    const QBlock& blk = it->second;
+    const int64_t off = (const char*)t.dst - (const char*)it->first;
+    const int N = t.N, K = t.K, col0 = (int)(off / K);
+    if (K != blk.K || off % K || col0 + N > blk.N)
+        throw std::runtime_error("internal: int8 block mismatch for tensor " + std::to_string(t.tid));
+    std::vector<int16_t> perm;
+    if (t.mode == PK_PLACE_SUBPERM) {  // columns (channel, freq) -> the engine's (freq, channel)
+        const int C = t.ld, F = t.row0;
+        perm.resize((size_t)N * K);
+        for (int r = 0; r < N; ++r)
+            for (int ch = 0; ch < C; ++ch)
+                for (int f = 0; f < F; ++f) perm[(size_t)r * K + f * C + ch] = q[(size_t)r * K + ch * F + f];
+        q = perm.data();
+    }
+    PkQHost h;
+    pk_i8_prepare_weight(q, N, K, scales, zps, n_scales, &h);
+    HIP_CHECK(hipMemcpyAsync(t.dst, h.w.data(), (size_t)N * K, hipMemcpyHostToDevice, st_));
+    HIP_CHECK(hipMemcpyAsync(blk.sw + col0, h.sw.data(), (size_t)N * 4, hipMemcpyHostToDevice, st_));
+    HIP_CHECK(hipMemcpyAsync(blk.zw + col0, h.zw.data(), (size_t)N * 4, hipMemcpyHostToDevice, st_));
+    HIP_CHECK(hipMemcpyAsync(blk.cs + col0, h.cs.data(), (size_t)N * 4, hipMemcpyHostToDevice, st_));
+    HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+void ParakeetEngine::set_tensor_q(int tid, const int16_t* q, int64_t n, const float* scales, const int32_t* zps,
+                                  int n_scales) {
+    auto it = table_.find(tid);
+    if (it == table_.end()) throw std::runtime_error("unknown Parakeet tensor id " + std::to_string(tid));
+    const TSpec& t = specs_[it->second];
+    if (t.dt != DT_I8) throw std::runtime_error("tensor " + std::to_string(tid) + " is not an int8 GEMM weight of this engine");
+    if (n != t.n)
+        throw std::runtime_error("tensor " + std::to_string(tid) + ": " + std::to_string(n) + " elements, expected " +
+                                 std::to_string(t.n));
+    if (n_scales != 1 && n_scales != t.N) throw std::runtime_error("tensor " + std::to_string(tid) + ": bad scale count");
+    select();
+    place_q(t, q, scales, zps, n_scales);
+}
+
 void ParakeetEngine::place(const TSpec& t, const float* src) {
+    if (t.dt == DT_I8) {  // quantised at load: symmetric, per tensor
+        std::vector<float> w((size_t)t.n);
+        HIP_CHECK(hipMemcpyAsync(w.data(), src, (size_t)t.n * 4, hipMemcpyDeviceToHost, st_));
+        HIP_CHECK(hipStreamSynchronize(st_));
+        std::vector<int16_t> q;
+        float s;
+        pk_i8_quantize_weight(w.data(), t.n, &q, &s);
+        const int32_t z = 0;
+        place_q(t, q.data(), &s, &z, 1);
+        return;
+    }
     if (t.mode == PK_PLACE_LSTM) pk_place_lstm(src, dm_.pred, (float*)t.dst, t.row0, st_);
     else if (t.mode == PK_PLACE_BLOCKED) pk_place_blocked(src, t.N, t.K, t.dt, (float*)t.dst, st_);
     else if (t.mode == PK_PLACE_TRANSPOSE) pk_place(PK_PLACE_TRANSPOSE, DT_F32, src, t.N, t.K, t.dst, t.ld, t.row0, 0, 0, st_);
@@ -405,7 +599,8 @@ void ParakeetEngine::alloc_workspace() {
         ffh_ = c.take(M3 * dm_.ff * esz_);
         qkv_ = c.take(M3 * 3 * d * esz_);
         pe_ = c.take((int64_t)(2 * T3max_ - 1) * d * esz_);
-        pp_ = c.take((int64_t)(2 * T3max_ - 1) * Ln * d * esz_);
+        // int8 mode: linear_pos is quantised over each utterance's own positions, so projected per utterance
+        pp_ = c.take((int64_t)(dt_ == DT_I8 ? B : 1) * (2 * T3max_ - 1) * Ln * d * esz_);
         ctx_ = c.take(M3 * d * esz_);
         glu_ = c.take(M3 * 2 * d * esz_);
         cv_ = c.take(M3 * d * esz_);
@@ -424,6 +619,16 @@ void ParakeetEngine::alloc_workspace() {
         out_t1_ = (float*)c.take((int64_t)B * cap_ * 4);
         out_t2_ = (float*)c.take((int64_t)B * cap_ * 4);
         dsum_ = (double*)c.take(16);
+        if (dt_ == DT_I8) {
+            const int64_t rows2 = (int64_t)B * T2max_ * F2_, rowsp = (int64_t)B * (2 * T3max_ - 1);
+            const int64_t qa = std::max(std::max(rows2 * C, M3 * std::max(dm_.ff, F3_ * C)), rowsp * d);
+            qa_ = (int8_t*)c.take(qa);
+            qrow_ = (int*)c.take(std::max(rows2, rowsp) * 4);
+            qslots_ = 4 + 9 * Ln;  // quantised GEMMs per encoder pass
+            qkeys_ = (unsigned*)c.take((int64_t)qslots_ * B * 8);
+            qsa_ = (float*)c.take(B * 4);
+            qza_ = (int*)c.take(B * 4);
+        }
         if (!pass) {
             abytes_ = c.off;
             if (hipMalloc(&aarena_, abytes_) != hipSuccess) {
@@ -504,6 +709,7 @@ void ParakeetEngine::run_mel(const float* pcm_dev, int64_t stride, int B, int Tp
 // Returns the split used.
 int ParakeetEngine::gemm(int dt, int epi, const void* A, int lda, const void* W, int ldw, int M, int N, int K,
                          const float* bias, void* Cp, int ldc, float alpha) {
+    if (dt == DT_I8) return gemm_i8(epi, (const float*)A, lda, W, M, N, K, bias, (float*)Cp, ldc, alpha);
     // SPT_GEMM_T256 / SPT_GEMM_T64 / SPT_NO_SKINNY: read per call so tests can pin each variant
     // (eager calls only: a captured encoder graph keeps the variants it was captured with)
     const char* t256e = getenv("SPT_GEMM_T256");
@@ -541,22 +747,75 @@ int ParakeetEngine::gemm(int dt, int epi, const void* A, int lda, const void* W,
     return ks;
 }
 
+// int8 mode: quantise the input per utterance (qg_: how its rows split into utterances), then the
+// int8 MFMA GEMM; residual products go to slab 0 whole (integers are not split over K)
+int ParakeetEngine::gemm_i8(int epi, const float* A, int lda, const void* W, int M, int N, int K, const float* bias,
+                            float* Cp, int ldc, float alpha) {
+    auto it = qblk_.find(W);
+    if (it == qblk_.end() || it->second.N != N || it->second.K != K || lda != K || M != qB_ * qg_.rows || qslot_ >= qslots_)
+        throw std::runtime_error("internal: int8 GEMM without a matching weight block or row grouping");
+    const QBlock& blk = it->second;
+    unsigned* keys = qkeys_ + (size_t)(qslot_++) * max_batch_ * 2;
+    pk_i8_minmax(A, K, qg_, qB_, keys, st_);
+    pk_i8_quantize(A, K, qg_, qB_, keys, qa_, qrow_, qsa_, qza_, st_);
+    PkI8Gemm g{};
+    g.Q = qa_; g.rowsum = qrow_; g.sa = qsa_; g.za = qza_; g.rows = qg_.rows;
+    g.W = (const int8_t*)W; g.sw = blk.sw; g.zw = blk.zw; g.cs = blk.cs;
+    g.M = M; g.N = N; g.K = K;
+    g.bias = epi == EPI_PARTIAL ? nullptr : bias;
+    g.act = epi == EPI_BIAS_RELU ? PK_I8_RELU : epi == EPI_BIAS_SWISH ? PK_I8_SWISH : PK_I8_NONE;
+    g.alpha = epi == EPI_BIAS_F32 ? alpha : 1.0f;
+    g.C = Cp; g.ldc = ldc;
+    pk_i8_gemm(g, st_);
+    if (tap_.armed)
+        for (const QTap& t : blk.taps)
+            if (t.tid == tap_.tid) {  // the first utterance's rows (debug_encode runs one)
+                const int rows = qg_.rows;
+                tap_.M = rows; tap_.K = K; tap_.N = t.n; tap_.bias_included = g.bias != nullptr;
+                tap_.a.resize((size_t)rows * K);
+                tap_.y.resize((size_t)rows * t.n);
+                HIP_CHECK(hipMemcpyAsync(tap_.a.data(), A, tap_.a.size() * 4, hipMemcpyDeviceToHost, st_));
+                HIP_CHECK(hipMemcpy2DAsync(tap_.y.data(), (size_t)t.n * 4, Cp + t.col0, (size_t)ldc * 4, (size_t)t.n * 4,
+                                           rows, hipMemcpyDeviceToHost, st_));
+                HIP_CHECK(hipStreamSynchronize(st_));
+                tap_.armed = false;
+                tap_.done = true;
+            }
+    return 1;
+}
+
 void ParakeetEngine::run_encoder(int B, int Tp, int T1p, int T2p, int T3p) {
     const int C = dm_.sub_ch, d = dm_.d, H = dm_.n_heads, dk = d / H, ff = dm_.ff, Ln = dm_.n_layers;
+    const bool i8 = dt_ == DT_I8;
+    // int8 mode: how the next GEMMs' input rows split into utterances (the quantisation ranges)
+    auto grp = [&](int mode, int rows, int rpf, int stage) {
+        qg_ = PkI8Groups{mode, rows, rpf, lens_, 4, stage};
+        qB_ = B;
+    };
+    if (i8) {
+        qslot_ = 0;
+        HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)qkeys_, (int)0x80000000u, (size_t)qslots_ * max_batch_ * 2, st_));
+    }
     // ---- dw_striding subsampling (channel-last activations)
-    pk_conv0(dt_, mel_, lens_, B, Tp, dm_.n_mels, c0_w_, c0_b_, C, y1_, T1p, F1_, st_);
-    pk_dwconv(dt_, y1_, lens_, 1, B, T1p, F1_, dw1_w_, dw1_b_, C, y2a_, T2p, F2_, st_);
+    pk_conv0(adt_, mel_, lens_, B, Tp, dm_.n_mels, c0_w_, c0_b_, C, y1_, T1p, F1_, st_);
+    pk_dwconv(adt_, y1_, lens_, 1, B, T1p, F1_, dw1_w_, dw1_b_, C, y2a_, T2p, F2_, st_);
+    grp(PK_I8_ROWS, T2p * F2_, F2_, 2);
     gemm(dt_, EPI_BIAS_RELU, y2a_, C, pw1_w_, C, B * T2p * F2_, C, C, pw1_b_, y2_, C);
-    pk_dwconv(dt_, y2_, lens_, 2, B, T2p, F2_, dw2_w_, dw2_b_, C, y3a_, T3p, F3_, st_);
+    pk_dwconv(adt_, y2_, lens_, 2, B, T2p, F2_, dw2_w_, dw2_b_, C, y3a_, T3p, F3_, st_);
+    grp(PK_I8_ROWS, T3p * F3_, F3_, 3);
     gemm(dt_, EPI_BIAS_RELU, y3a_, C, pw2_w_, C, B * T3p * F3_, C, C, pw2_b_, y3_, C);
     float* x = x_;
     float* x2 = x_ + (int64_t)max_batch_ * T3max_ * d;
     const int M = B * T3p;
+    grp(PK_I8_ROWS, T3p, 1, 3);
     gemm(dt_, EPI_BIAS_F32, y3_, F3_ * C, sub_w_, F3_ * C, M, d, F3_ * C, sub_b_, x, d, sqrtf((float)d));
     mark(PK_ST_SUB);
     // ---- relative positions, projected for every layer at once
-    pk_relpos(dt_, T3p, d, pe_, st_);
-    gemm(dt_, EPI_BIAS, pe_, d, pos_w_, d, 2 * T3p - 1, Ln * d, d, nullptr, pp_, Ln * d);
+    pk_relpos(adt_, T3p, d, pe_, st_);
+    // (int8 mode: one projection per utterance, quantised over its own positions |r| < T3_b)
+    grp(PK_I8_POS, 2 * T3p - 1, 1, 3);
+    gemm(dt_, EPI_BIAS, pe_, d, pos_w_, d, (i8 ? B : 1) * (2 * T3p - 1), Ln * d, d, nullptr, pp_, Ln * d);
+    grp(PK_I8_ROWS, T3p, 1, 3);
     mark(PK_ST_POS);
     const int64_t sst = (int64_t)M * d;
     int ks;
@@ -565,33 +824,33 @@ void ParakeetEngine::run_encoder(int B, int Tp, int T1p, int T2p, int T3p) {
         // 1/2 FFN; its product stays pending in the slabs until the next LayerNorm (the first
         // block's input LayerNorm here, the others' in the previous block's output LayerNorm)
         if (l == 0) {
-            layernorm(dt_, x, M, d, y.ln1_w, y.ln1_b, xn_, st_);
+            layernorm(adt_, x, M, d, y.ln1_w, y.ln1_b, xn_, st_);
             mark(PK_ST_LN);
         }
         gemm(dt_, EPI_BIAS_SWISH, xn_, d, y.ff1_w1, d, M, ff, d, y.ff1_b1, ffh_, ff);
         ks = gemm(dt_, EPI_PARTIAL, ffh_, ff, y.ff1_w2, ff, M, d, ff, nullptr, slab_, d);
         mark(PK_ST_FFN);
         // rel-pos MHSA
-        layernorm_pend(dt_, x, M, d, slab_, ks, sst, y.ff1_b2, 0.5f, y.lna_w, y.lna_b, xn_, true, st_);
+        layernorm_pend(adt_, x, M, d, slab_, ks, sst, y.ff1_b2, 0.5f, y.lna_w, y.lna_b, xn_, true, st_);
         mark(PK_ST_LN);
         gemm(dt_, EPI_BIAS, xn_, d, y.qkv_w, d, M, 3 * d, d, y.qkv_b, qkv_, 3 * d);
         mark(PK_ST_QKVO);
-        pk_rel_attn(dt_, qkv_, (const char*)pp_ + (size_t)l * d * esz_, Ln * d, y.pos_u, y.pos_v, lens_, B, T3p, H, dk,
-                    ctx_, st_);
+        pk_rel_attn(adt_, qkv_, (const char*)pp_ + (size_t)l * d * esz_, Ln * d, y.pos_u, y.pos_v, lens_, B, T3p, H, dk,
+                    ctx_, st_, i8 ? (int64_t)(2 * T3p - 1) * Ln * d : 0);
         mark(PK_ST_ATTN);
         ks = gemm(dt_, EPI_PARTIAL, ctx_, d, y.o_w, d, M, d, d, nullptr, slab_, d);
         mark(PK_ST_QKVO);
         // convolution module
-        layernorm_pend(dt_, x, M, d, slab_, ks, sst, y.o_b, 1.0f, y.lnc_w, y.lnc_b, xn_, true, st_);
+        layernorm_pend(adt_, x, M, d, slab_, ks, sst, y.o_b, 1.0f, y.lnc_w, y.lnc_b, xn_, true, st_);
         mark(PK_ST_LN);
         gemm(dt_, EPI_BIAS, xn_, d, y.pw1_w, d, M, 2 * d, d, y.pw1_b, glu_, 2 * d);
         mark(PK_ST_CONV_PW);
-        pk_conv_module(dt_, glu_, lens_, B, T3p, d, dm_.conv_k, y.dw_w, y.dw_b, y.bn_g, y.bn_b, y.bn_m, y.bn_v, cv_, st_);
+        pk_conv_module(adt_, glu_, lens_, B, T3p, d, dm_.conv_k, y.dw_w, y.dw_b, y.bn_g, y.bn_b, y.bn_m, y.bn_v, cv_, st_);
         mark(PK_ST_CONV_DW);
         ks = gemm(dt_, EPI_PARTIAL, cv_, d, y.pw2_w, d, M, d, d, nullptr, slab_, d);
         mark(PK_ST_CONV_PW);
         // 1/2 FFN
-        layernorm_pend(dt_, x, M, d, slab_, ks, sst, y.pw2_b, 1.0f, y.ln2_w, y.ln2_b, xn_, true, st_);
+        layernorm_pend(adt_, x, M, d, slab_, ks, sst, y.pw2_b, 1.0f, y.ln2_w, y.ln2_b, xn_, true, st_);
         mark(PK_ST_LN);
         gemm(dt_, EPI_BIAS_SWISH, xn_, d, y.ff2_w1, d, M, ff, d, y.ff2_b1, ffh_, ff);
         ks = gemm(dt_, EPI_PARTIAL, ffh_, ff, y.ff2_w2, ff, M, d, ff, nullptr, slab_, d);
@@ -599,7 +858,7 @@ void ParakeetEngine::run_encoder(int B, int Tp, int T1p, int T2p, int T3p) {
         // LayerNorm out (f32) of x + the pending 1/2 FFN into the other residual buffer, and with
         // it the next block's input LayerNorm
         if (l + 1 < Ln)
-            layernorm_pend2(dt_, x, M, d, slab_, ks, sst, y.ff2_b2, 0.5f, y.lno_w, y.lno_b, x2, L_[l + 1].ln1_w,
+            layernorm_pend2(adt_, x, M, d, slab_, ks, sst, y.ff2_b2, 0.5f, y.lno_w, y.lno_b, x2, L_[l + 1].ln1_w,
                             L_[l + 1].ln1_b, xn_, st_);
         else
             layernorm_pend(DT_F32, x, M, d, slab_, ks, sst, y.ff2_b2, 0.5f, y.lno_w, y.lno_b, x2, false, st_);
@@ -893,9 +1152,27 @@ void ParakeetEngine::debug_encode(const float* mel_host, int T, float* out_host)
         for (int j = 0; j < dm_.n_mels; ++j) tmp[(size_t)t * dm_.n_mels + j] = mel_host[(size_t)j * T + t];
     HIP_CHECK(hipMemcpyAsync(lens_, lens, 16, hipMemcpyHostToDevice, st_));
     HIP_CHECK(hipMemcpyAsync(mel_, tmp.data(), tmp.size() * 4, hipMemcpyHostToDevice, st_));
-    run_encoder(1, T, T1, T2, T3);
+    tap_.armed = tap_.tid >= 0 && !tap_.done;
+    try {
+        run_encoder(1, T, T1, T2, T3);
+    } catch (...) {
+        tap_.armed = false;
+        throw;
+    }
+    tap_.armed = false;
     HIP_CHECK(hipMemcpyAsync(out_host, enc_out_, (size_t)T3 * dm_.d * 4, hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
+}
+
+bool ParakeetEngine::debug_tap(int tid) {
+    for (auto& kv : qblk_)
+        for (const QTap& t : kv.second.taps)
+            if (t.tid == tid) {
+                tap_ = Tap{};
+                tap_.tid = tid;
+                return true;
+            }
+    return false;
 }
 
 int ParakeetEngine::debug_last_encoder(int b, float* out_host) {
@@ -933,6 +1210,7 @@ bool ParakeetEngine::debug_weight_checksum(int tid, double* out2) {
     if (it == table_.end()) return false;
     const TSpec& t = specs_[it->second];
     if (t.mode == PK_PLACE_TRANSPOSE || t.mode == PK_PLACE_LSTM || t.mode == PK_PLACE_BLOCKED) return false;  // re-tiled
+    if (t.dt == DT_I8) return false;  // stored as integers
     select();
     HIP_CHECK(hipMemsetAsync(dsum_, 0, 16, st_));
     tensor_checksum(t.dt, t.dst, t.n, dsum_, st_);

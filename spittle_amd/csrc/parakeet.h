@@ -8,9 +8,11 @@
 #include <stdint.h>
 
 #include <map>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "kernels.h"
 #include "pk_kernels.h"
 
 namespace spt {
@@ -38,6 +40,29 @@ struct PkTimings {
     double mel_ms = 0, encoder_ms = 0, decode_ms = 0, total_ms = 0, h2d_ms = 0;
     int n_steps = 0, batch = 0, enc_frames = 0;
 };
+
+// a model the engine cannot run in the requested mode (SPT_ERR_UNSUPPORTED)
+struct PkUnsupported : std::runtime_error {
+    using std::runtime_error::runtime_error;
+};
+
+// ---- int8 mode (dtype DT_I8): host-side weight preparation
+struct PkQHost {
+    std::vector<int8_t> w;      // [N][K]: the stored integers minus `shift` (128 for uint8 weights)
+    std::vector<float> sw;      // per output column: scale
+    std::vector<int> zw, cs;    // per output column: zero point - shift, sum_k w[n][k]
+};
+// stored integers [N][K] (int8 or uint8 values, widened) + their scales / zero points (one, or one
+// per output channel) -> the GEMM's operands; nothing is requantised
+void pk_i8_prepare_weight(const int16_t* q, int N, int K, const float* scales, const int32_t* zps, int n_scales,
+                          PkQHost* out);
+// an f32 weight -> symmetric per-tensor int8: s = max|w| / 127, q = clamp(rint(w / s), -127, 127)
+void pk_i8_quantize_weight(const float* w, int64_t n, std::vector<int16_t>* q, float* scale);
+// the three int8 kernels on host data, without a model (tests): A [M][K] split into row groups
+// (utterances) of group_len rows; out: q [M][K], sa / za per group, acc [M][N], y [M][N]
+void pk_i8_debug_gemm(int device, const float* A, int M, int K, const int* group_len, int n_groups, const int16_t* W,
+                      int N, const float* scales, const int32_t* zps, int n_scales, const float* bias, int act,
+                      uint8_t* q_out, float* sa_out, int32_t* za_out, int32_t* acc_out, float* y_out);
 
 class ParakeetEngine {
 public:
@@ -71,6 +96,24 @@ public:
         return v;
     }
     int64_t tensor_numel(int tid) const;
+    // int8 mode: a quantised layer's weight as its stored integers [N][K] (NeMo orientation, int8
+    // or uint8 values) with their scale(s) and zero point(s); throws for any other tensor or mode
+    void set_tensor_q(int tid, const int16_t* q, int64_t n, const float* scales, const int32_t* zps, int n_scales);
+    bool is_q_weight(int tid) const {
+        auto it = table_.find(tid);
+        return it != table_.end() && specs_[it->second].dt == DT_I8;
+    }
+    // int8 mode test hook: capture, in the next debug_encode, the quantised GEMM whose weight is
+    // tensor `tid` (the stacked q / k / v GEMM is named by linear_q): its f32 input rows [M][K] and
+    // its stored f32 output [M][N]; false if tid names no quantised GEMM of this engine
+    struct Tap {
+        int tid = -1;
+        bool armed = false, done = false;
+        int M = 0, K = 0, N = 0, bias_included = 0;
+        std::vector<float> a, y;
+    };
+    bool debug_tap(int tid);
+    const Tap& tap() const { return tap_; }
 
     // B utterances, pcm_dev + b * stride (device); n[b] <= max_samples
     void transcribe_device(const float* pcm_dev, int64_t stride, const int* n, int B, int max_symbols,
@@ -103,6 +146,12 @@ private:
         float *ln2_w, *ln2_b; void *ff2_w1; float* ff2_b1; void* ff2_w2; float* ff2_b2;
         float *lno_w, *lno_b;
     };
+    struct QTap { int tid, col0, n; };  // a tap site: the GEMM's output columns [col0, col0 + n)
+    struct QBlock {                     // int8 mode: one GEMM's weight block, keyed by its device pointer
+        float* sw; int* zw; int* cs;    // per output column
+        int N, K;
+        std::vector<QTap> taps;
+    };
     struct GraphKey {  // decode-step graphs: shape-free in the utterance length (PkState::t3p)
         int B, max_symbols;
         bool operator<(const GraphKey& o) const {
@@ -118,6 +167,9 @@ private:
     void set_frame_limits();  // Tmax_ .. T3max_, cap_ from max_samples_
     void upload_tables();
     void place(const TSpec& t, const float* src_dev);
+    void place_q(const TSpec& t, const int16_t* q, const float* scales, const int32_t* zps, int n_scales);
+    int gemm_i8(int epi, const float* A, int lda, const void* W, int M, int N, int K, const float* bias, float* Cp,
+                int ldc, float alpha);
     void frame_counts(const int* n, int B, std::vector<int>* lens, int* Tp, int* T1p, int* T2p, int* T3p) const;
     void run_mel(const float* pcm_dev, int64_t stride, int B, int Tp);
     void run_encoder(int B, int Tp, int T1p, int T2p, int T3p);
@@ -130,7 +182,8 @@ private:
     PkDims dm_;
     int dt_, dev_, max_batch_, max_samples_;
     uint64_t seed_;
-    int esz_;
+    int adt_;                        // activation dtype (dt_; f32 in the int8 mode)
+    int esz_, wesz_;                 // activation / GEMM weight element size
     int F1_, F2_, F3_;               // frequency bins after each stride-2 stage
     int Tmax_, T1max_, T2max_, T3max_;
     int P_pad_, joint_pad_, joint_tiles_;  // W^T row lengths (multiples of 64), joint workgroups
@@ -191,6 +244,16 @@ private:
     float* scratch_ = nullptr;       // f32 staging of one weight tensor
     int64_t scratch_n_ = 0;
     double* dsum_ = nullptr;
+    // ---- int8 mode
+    std::map<const void*, QBlock> qblk_;
+    int8_t* qa_ = nullptr;           // the current GEMM's quantised input (q - 128)
+    int* qrow_ = nullptr;            // its row sums
+    unsigned* qkeys_ = nullptr;      // [qslots_][max_batch][2] range keys, one slot per GEMM of a pass
+    float* qsa_ = nullptr;           // the current GEMM's per-utterance scale / zero point
+    int* qza_ = nullptr;
+    int qslots_ = 0, qslot_ = 0, qB_ = 0;
+    PkI8Groups qg_{};
+    Tap tap_;
     std::map<GraphKey, hipGraphExec_t> graphs_;
     std::map<std::pair<int, int>, hipGraphExec_t> enc_graphs_;  // (B, Tp) -> encoder graph
     std::map<std::pair<int, int>, int> enc_seen_;

@@ -31,8 +31,9 @@ void pk_dwconv(int dtype, const void* x, const int* lens, int stage, int B, int 
 void pk_relpos(int dtype, int Tp, int d, void* pe, hipStream_t st);
 // rel-pos multi-head attention: qkv [B*Tp][3d] (q | k | v), p [2Tp-1][ldp] (layer slice of the
 // projected positions), u / v biases [H][dk]; keys >= T3_b masked; out [B*Tp][d]
+// p_bstride != 0 (f32 only): utterance b reads its own projected positions at p + b * p_bstride
 void pk_rel_attn(int dtype, const void* qkv, const void* p, int ldp, const float* pu, const float* pv,
-                 const int* lens, int B, int Tp, int H, int dk, void* out, hipStream_t st);
+                 const int* lens, int B, int Tp, int H, int dk, void* out, hipStream_t st, int64_t p_bstride = 0);
 // conformer convolution module after pw1: a [B*Tp][2d] -> GLU -> depthwise K taps (frames
 // outside [0, T3_b) zero) -> BatchNorm (eval) -> Swish -> out [B*Tp][d]
 void pk_conv_module(int dtype, const void* a, const int* lens, int B, int Tp, int d, int K, const float* dw_w,
@@ -45,6 +46,38 @@ enum { PK_PLACE_COPY = 0, PK_PLACE_TRANSPOSE = 1, PK_PLACE_SUBPERM = 2, PK_PLACE
 // SUBPERM: src [N][C * F] (channel-major flatten) -> dst [N][F * C] (dtype)
 void pk_place(int mode, int dtype, const float* src, int N, int K, void* dst, int ld, int row0, int C, int F,
               hipStream_t st);
+
+// ---- int8 mode (k_pk_i8.hip): DynamicQuantizeLinear + MatMulInteger, DESIGN.md §9.7
+// The rows of a quantised GEMM's input in utterances ("groups"): group g owns rows
+// [g * rows, (g + 1) * rows), of which the first lens[g * lens_stride + lens_off] * rpf are valid
+// and set the group's range (lens == nullptr: all of them).  PK_I8_POS: every group reads the same
+// table A of `rows` = 2 Tp - 1 relative positions, of which its own |r| < len set its range.
+enum { PK_I8_ROWS = 0, PK_I8_POS = 1 };
+struct PkI8Groups {
+    int mode, rows, rpf;
+    const int* lens; int lens_stride, lens_off;
+};
+// keys[g][2] (preset to the key of 0.0f, 0x80000000) <- min(0, min x), max(0, max x) of group g
+void pk_i8_minmax(const float* A, int K, const PkI8Groups& G, int n_groups, unsigned* keys, hipStream_t st);
+// Q [n_groups * rows][K] = q - 128, rowsum[m] = sum_k Q[m][k]; sa[g], za[g] = the group's scale and
+// zero point (a zero range gives scale 0 and q = 0)
+void pk_i8_quantize(const float* A, int K, const PkI8Groups& G, int n_groups, const unsigned* keys, int8_t* Q,
+                    int* rowsum, float* sa, int* za, hipStream_t st);
+enum { PK_I8_NONE = 0, PK_I8_RELU = 1, PK_I8_SWISH = 2 };
+struct PkI8Gemm {
+    const int8_t* Q; const int* rowsum;  // quantised input [M][K] (q - 128) and its row sums
+    const float* sa; const int* za;      // per group (row m belongs to group m / rows)
+    int rows;
+    const int8_t* W;                     // [N][K]: w - shift (shift 128 for uint8 weights, else 0)
+    const float* sw; const int* zw;      // per column: scale, zero point - shift
+    const int* cs;                       // per column: sum_k W[n][k]
+    int M, N, K;
+    const float* bias;                   // [N] or nullptr
+    int act; float alpha;                // y = act(float(acc) * (sa * sw) + bias) * alpha
+    float* C; int ldc;
+    int* acc_out;                        // [M][N] int32 accumulators (tests) or nullptr
+};
+void pk_i8_gemm(const PkI8Gemm& a, hipStream_t st);
 
 // ---- TDT greedy decoding (f32 prediction network + joint)
 struct PkState {         // per row, device

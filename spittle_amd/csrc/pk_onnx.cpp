@@ -35,6 +35,11 @@ namespace {
 struct Val {
     std::vector<int64_t> dims;
     std::vector<float> v;
+    // a quantised initializer also keeps what the file stores: its integers (same order as v) with
+    // their scales and zero points (one, or one per output channel)
+    std::vector<int16_t> q;
+    std::vector<float> qs;
+    std::vector<int32_t> qz;
 };
 
 std::vector<std::string> tokens(const std::string& s) {
@@ -151,6 +156,13 @@ Val transpose2(const Val& a) {
     t.v.resize(a.v.size());
     for (int64_t r = 0; r < R; ++r)
         for (int64_t c = 0; c < C; ++c) t.v[(size_t)c * R + r] = a.v[(size_t)r * C + c];
+    if (!a.q.empty()) {
+        t.q.resize(a.q.size());
+        for (int64_t r = 0; r < R; ++r)
+            for (int64_t c = 0; c < C; ++c) t.q[(size_t)c * R + r] = a.q[(size_t)r * C + c];
+        t.qs = a.qs;
+        t.qz = a.qz;
+    }
     return t;
 }
 
@@ -163,6 +175,11 @@ bool dequant(const onnx::Tensor& q, const onnx::Tensor& sc, const onnx::Tensor* 
     if (z.size() != s.size() || s.empty()) { *err = "quantised tensor '" + q.name + "': scale / zero point sizes differ"; return false; }
     out->dims = q.dims;
     out->v.resize(qv.size());
+    if (q.data_type == onnx::T_INT8 || q.data_type == onnx::T_UINT8) {
+        out->q.assign(qv.begin(), qv.end());
+        out->qs = s;
+        out->qz.assign(z.begin(), z.end());
+    }
     if (s.size() == 1) {
         for (size_t i = 0; i < qv.size(); ++i) out->v[i] = (qv[i] - z[0]) * s[0];
         return true;
@@ -267,14 +284,24 @@ bool map_graph(const onnx::Model& m, Mapper* mp, int* n_q, std::string* err) {
         auto in = [&](size_t i) -> const Val* { return i < n.inputs.size() ? find_val(vals, n.inputs[i]) : nullptr; };
         if (op == "MatMul" || op == "MatMulInteger" || op == "MatMulIntegerToFloat") {
             const Val* w = in(1);
-            if (w && w->dims.size() == 2) PUT(mp->lookup(path + ".weight"), transpose2(*w), err, n.name);
+            if (w && w->dims.size() == 2) {
+                Val t = transpose2(*w);
+                // the integers are the model's only where the node multiplies integers; a per-channel
+                // weight keeps them when its channels are the output columns
+                if (op != "MatMulInteger" || (t.qs.size() != 1 && (int64_t)t.qs.size() != t.dims[0])) t.q.clear();
+                PUT(mp->lookup(path + ".weight"), std::move(t), err, n.name);
+            }
         } else if (op == "Gemm") {
             const onnx::Attribute* tb = n.attr("transB");
             if (const Val* w = in(1); w && w->dims.size() == 2)
                 PUT(mp->lookup(path + ".weight"), tb && tb->i ? *w : transpose2(*w), err, n.name);
             if (const Val* b = in(2)) PUT(mp->lookup(path + ".bias"), *b, err, n.name);
         } else if (op == "Conv" || op == "ConvInteger") {
-            if (const Val* w = in(1)) PUT(mp->lookup(path + ".weight"), *w, err, n.name);
+            if (const Val* w = in(1)) {
+                Val t = *w;
+                if (op != "ConvInteger" || (t.qs.size() != 1 && (t.dims.empty() || (int64_t)t.qs.size() != t.dims[0]))) t.q.clear();
+                PUT(mp->lookup(path + ".weight"), std::move(t), err, n.name);
+            }
             if (op == "Conv")
                 if (const Val* b = in(2)) PUT(mp->lookup(path + ".bias"), *b, err, n.name);
         } else if (op == "LayerNormalization") {
@@ -343,7 +370,11 @@ bool map_graph(const onnx::Model& m, Mapper* mp, int* n_q, std::string* err) {
     // parameters consumed by ops the node pass does not know keep their state-dict names
     for (auto& kv : vals) {
         const int tid = mp->lookup(kv.first);
-        if (tid >= 0 && !mp->assigned.count(tid)) PUT(tid, kv.second, err, kv.first);
+        if (tid >= 0 && !mp->assigned.count(tid)) {
+            Val t = kv.second;
+            t.q.clear();  // no integer op consumes it
+            PUT(tid, std::move(t), err, kv.first);
+        }
     }
     return true;
 }
@@ -496,7 +527,15 @@ bool load_parakeet_onnx(const std::string& dir, PkOnnxModel* out, std::string* e
         }
     }
     out->dims = d;
-    for (auto& kv : t) out->tensors[kv.first] = std::move(kv.second.v);
+    for (auto& kv : t) {
+        if (!kv.second.q.empty()) {
+            PkOnnxQTensor& qt = out->qtensors[kv.first];
+            qt.q = std::move(kv.second.q);
+            qt.scales = std::move(kv.second.qs);
+            qt.zero_points = std::move(kv.second.qz);
+        }
+        out->tensors[kv.first] = std::move(kv.second.v);
+    }
     const std::string voc = dir + "/vocab.txt";
     if (file_exists(voc) && !read_vocab(voc, d.n_vocab, &out->pieces, err)) return false;
     return true;

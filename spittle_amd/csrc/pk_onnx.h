@@ -14,9 +14,18 @@
 
 namespace spt {
 
+// a weight consumed by MatMulInteger / ConvInteger, as the file stores it: the integers in the
+// engine's [N][K] orientation (int8 or uint8 values, widened), scales and zero points (one, or N)
+struct PkOnnxQTensor {
+    std::vector<int16_t> q;
+    std::vector<float> scales;
+    std::vector<int32_t> zero_points;
+};
+
 struct PkOnnxModel {
     PkDims dims;
     std::map<int, std::vector<float>> tensors;  // engine tensor id -> f32 values in NeMo's layout
+    std::map<int, PkOnnxQTensor> qtensors;      // ... -> the stored integers, for the int8 engine mode
     std::vector<std::string> pieces;            // vocab.txt: token id -> piece (blank excluded)
     std::string encoder_file, decoder_file;
     int n_quantized = 0;                        // initializers dequantized (int8 / uint8 + scale + zero point)

@@ -41,7 +41,7 @@ class TimestampGranularity(enum.IntEnum):
 
 @dataclass
 class ParakeetModelParams:
-    dtype: str = "f16"            # "f16" (BASELINE config: fp16 encoder) | "f32" | "bf16"
+    dtype: str = "f16"            # "f16" (BASELINE config: fp16 encoder) | "f32" | "bf16" | "i8"
     device: int = 0
     max_batch: int = 8
     max_seconds: float = 30.0     # chunk length of one device pass
@@ -52,6 +52,12 @@ class ParakeetModelParams:
         """The app's choice (transcription.rs:281): the int8 export's weights are dequantised at load
         and the network runs with an fp16 encoder."""
         return ParakeetModelParams()
+
+    @staticmethod
+    def int8_exact() -> "ParakeetModelParams":
+        """The int8 export's own arithmetic: every encoder Linear and pointwise
+        convolution as DynamicQuantizeLinear -> MatMulInteger on the stored integers; the rest f32."""
+        return ParakeetModelParams(dtype="i8")
 
     @staticmethod
     def fp32() -> "ParakeetModelParams":
@@ -71,7 +77,7 @@ class ParakeetResult(TranscriptionResult):
     n_chunks: int = 0
 
 
-_DT = {"f32": L.SPT_DTYPE_F32, "bf16": L.SPT_DTYPE_BF16, "f16": L.SPT_DTYPE_F16}
+_DT = {"f32": L.SPT_DTYPE_F32, "bf16": L.SPT_DTYPE_BF16, "f16": L.SPT_DTYPE_F16, "i8": L.SPT_DTYPE_I8}
 
 
 def _check(lib, ctx, st):
@@ -203,6 +209,21 @@ class ParakeetEngine:
         _check(self._lib, self._ctx, self._lib.spt_parakeet_debug_encode(self._need(), mel.ctypes.data_as(C.POINTER(C.c_float)),
                                                                          T, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
+
+    def debug_tap(self, tid: int) -> None:
+        """int8 mode: capture, in the next debug_encode, the quantised GEMM whose weight is tensor tid."""
+        _check(self._lib, self._ctx, self._lib.spt_parakeet_debug_tap(self._need(), int(tid)))
+
+    def debug_tap_read(self):
+        """-> (a [M][K] the tapped GEMM's f32 input rows, y [M][N] its stored f32 output, bias_included)"""
+        dims = (C.c_int32 * 4)()
+        _check(self._lib, self._ctx, self._lib.spt_parakeet_debug_tap_read(self._need(), dims, None, 0, None, 0))
+        M, K, N, bias = (int(v) for v in dims)
+        a, y = np.empty((M, K), np.float32), np.empty((M, N), np.float32)
+        fp = C.POINTER(C.c_float)
+        _check(self._lib, self._ctx, self._lib.spt_parakeet_debug_tap_read(
+            self._need(), dims, a.ctypes.data_as(fp), a.size, y.ctypes.data_as(fp), y.size))
+        return a, y, bool(bias)
 
     def debug_decode(self, enc: np.ndarray, max_symbols: int = 10) -> ParakeetResult:
         enc = np.ascontiguousarray(enc, dtype=np.float32)
@@ -340,6 +361,17 @@ class OnnxModelDir:
         n = self._lib.spt_parakeet_onnx_tensor(self._h, int(tid), C.byref(p))
         return None if n < 0 else np.ctypeslib.as_array(p, shape=(n,)).copy()
 
+    def qtensor(self, tid: int):
+        """A MatMulInteger / ConvInteger weight as stored: (integers [n] in the engine's [N][K] order
+        as int16, scales, zero points), or None for a tensor no integer op consumes."""
+        q, s, z = C.POINTER(C.c_int16)(), C.POINTER(C.c_float)(), C.POINTER(C.c_int32)()
+        ns = C.c_int32()
+        n = self._lib.spt_parakeet_onnx_qtensor(self._h, int(tid), C.byref(q), C.byref(s), C.byref(z), C.byref(ns))
+        if n < 0:
+            return None
+        return (np.ctypeslib.as_array(q, shape=(n,)).copy(), np.ctypeslib.as_array(s, shape=(ns.value,)).copy(),
+                np.ctypeslib.as_array(z, shape=(ns.value,)).copy())
+
     def piece(self, i: int) -> Optional[str]:
         s = self._lib.spt_parakeet_onnx_piece(self._h, int(i))
         return None if s is None else s.decode()
@@ -420,3 +452,32 @@ def _sentencepiece_pieces(model_bytes: bytes) -> List[str]:
     import sentencepiece as spm
     sp = spm.SentencePieceProcessor(model_proto=model_bytes)
     return [sp.id_to_piece(i) for i in range(sp.get_piece_size())]
+
+
+PK_ACT = {None: 0, "relu": 1, "swish": 2}
+
+
+def debug_qgemm(a, group_len, w, w_scales, w_zero_points=None, bias=None, act=None, device: int = 0):
+    """The int8 mode's three kernels alone (spt_parakeet_debug_qgemm): a [M][K] f32 rows in row groups
+    (utterances) of group_len rows; w [N][K] stored integers (int8 or uint8 values) with one scale /
+    zero point, or N.  -> dict(q uint8 [M][K], sa [G], za [G], acc int32 [M][N], y f32 [M][N])."""
+    lib = L.load()
+    a = np.ascontiguousarray(a, np.float32)
+    w = np.ascontiguousarray(w, np.int16)
+    M, K = a.shape
+    N = w.shape[0]
+    gl = np.ascontiguousarray(group_len, np.int32)
+    sc = np.ascontiguousarray(np.atleast_1d(w_scales), np.float32)
+    zp = None if w_zero_points is None else np.ascontiguousarray(np.atleast_1d(w_zero_points), np.int32)
+    b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    out = dict(q=np.empty((M, K), np.uint8), sa=np.empty(gl.size, np.float32), za=np.empty(gl.size, np.int32),
+               acc=np.empty((M, N), np.int32), y=np.empty((M, N), np.float32))
+    ptr = lambda x, t: None if x is None else x.ctypes.data_as(C.POINTER(t))
+    err = C.create_string_buffer(512)
+    st = lib.spt_parakeet_debug_qgemm(device, ptr(a, C.c_float), M, K, ptr(gl, C.c_int32), gl.size, ptr(w, C.c_int16), N,
+                                      ptr(sc, C.c_float), ptr(zp, C.c_int32), sc.size, ptr(b, C.c_float), PK_ACT[act],
+                                      ptr(out["q"], C.c_uint8), ptr(out["sa"], C.c_float), ptr(out["za"], C.c_int32),
+                                      ptr(out["acc"], C.c_int32), ptr(out["y"], C.c_float), err, 512)
+    if st != L.SPT_OK:
+        raise TranscriptionError(st, err.value.decode())
+    return out
