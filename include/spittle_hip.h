@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define SPT_ABI_VERSION 13
+#define SPT_ABI_VERSION 14
 
 typedef enum {
     SPT_OK = 0,
@@ -46,7 +46,8 @@ typedef enum {
 } spt_status;
 
 typedef enum {
-    SPT_DTYPE_F32 = 0, SPT_DTYPE_BF16 = 1, SPT_DTYPE_F16 = 2 /* Parakeet only */,
+    SPT_DTYPE_F32 = 0, SPT_DTYPE_BF16 = 1,
+    SPT_DTYPE_F16 = 2 /* Parakeet; ABI 14: also spt_model_params.dtype, the Whisper fp16 engine */,
     SPT_DTYPE_I8 = 3 /* ABI 13, spt_pk_model_params.dtype only: the int8 ONNX export's arithmetic */
 } spt_dtype;
 
@@ -57,7 +58,16 @@ typedef enum {
 #define SPT_SUPPRESS_NST    8u  /* whisper_full_params.suppress_non_speech_tokens (ggml models) */
 
 typedef struct {
-    int32_t dtype;        /* spt_dtype: weights + activations (accumulation is always f32) */
+    int32_t dtype;        /* SPT_DTYPE_BF16 (default), SPT_DTYPE_F16 or SPT_DTYPE_F32: weights + activations at
+                             the GEMM / GEMV inputs (accumulation, residual stream, logits: always f32).
+                             ABI 14: SPT_DTYPE_F16 is an IEEE-half engine with the bf16 engine's layout and
+                             weight_bytes (spt_weights_export / _import work unchanged between two f16
+                             contexts); an f16 ggml file's matrices are held bit for bit, other types are
+                             dequantised in f32 and rounded once (nearest even, subnormals kept).
+                             Activations are not saturated (as in whisper.cpp), except that values
+                             stored into the decoder's K/V caches are clamped to +-65504 so a cache
+                             never holds Inf.  ABI <= 13 rejected SPT_DTYPE_F16 here (bad dtype).
+                             SPT_DTYPE_I8 is rejected. */
     int32_t device;       /* HIP device ordinal */
     int32_t max_batch;    /* utterance (30 s window) capacity per call */
     uint32_t flags;       /* SPT_MODEL_* (ABI <= 3: reserved, always 0) */

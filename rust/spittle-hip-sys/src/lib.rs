@@ -1,4 +1,4 @@
-//! Raw bindings to `include/spittle_hip.h` (ABI 13), the C boundary of the MI355X-native Whisper
+//! Raw bindings to `include/spittle_hip.h` (ABI 14), the C boundary of the MI355X-native Whisper
 //! and Parakeet-V3 backend.  One item per declaration of the header, same names, same layouts (x86-64 SysV; the
 //! layouts are checked field by field against gcc by tests/test_capi.py).  Safe wrappers live in
 //! the `spittle-hip` crate.
@@ -6,7 +6,7 @@
 
 use std::os::raw::{c_char, c_int, c_void};
 
-pub const SPT_ABI_VERSION: c_int = 13;
+pub const SPT_ABI_VERSION: c_int = 14;
 pub const SPT_PK_STAGE_COUNT: c_int = 9;
 
 pub type spt_status = c_int;
@@ -21,6 +21,7 @@ pub const SPT_ERR_INTERNAL: spt_status = 6;
 pub type spt_dtype = c_int;
 pub const SPT_DTYPE_F32: spt_dtype = 0;
 pub const SPT_DTYPE_BF16: spt_dtype = 1;
+/// Parakeet's default; ABI 14: also `spt_model_params.dtype`, the Whisper fp16 engine
 pub const SPT_DTYPE_F16: spt_dtype = 2;
 /// ABI 13, `spt_pk_model_params.dtype` only: the int8 ONNX export's own arithmetic
 pub const SPT_DTYPE_I8: spt_dtype = 3;

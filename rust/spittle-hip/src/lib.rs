@@ -1,5 +1,5 @@
 //! `HipWhisperEngine` and `HipParakeetEngine`: the `transcribe_rs::TranscriptionEngine` surfaces
-//! Spittle binds to, backed by the MI355X-native library (`libspittle_hip.so`, C ABI 13), plus `HipFrameResampler` and
+//! Spittle binds to, backed by the MI355X-native library (`libspittle_hip.so`, C ABI 14), plus `HipFrameResampler` and
 //! `HipSmoothedVad` (the capture-side resampler and voice-activity gate).
 //!
 //! What it replaces in the app (/root/reference/src-tauri/src/managers/transcription.rs):
@@ -35,6 +35,8 @@ use transcribe_rs::{TranscriptionEngine, TranscriptionResult, TranscriptionSegme
 /// bf16 weights on device 0, one utterance (and up to 7 more 30 s windows of it) per call.
 #[derive(Clone, Copy, Debug)]
 pub struct HipModelParams {
+    /// true: bf16 weights and activations; false: f32.  The fp16 engine (ABI 14) is asked for with
+    /// `HipWhisperEngine::load_model_f16` / `HipWhisperReplicas::load_f16`, which ignore this field.
     pub bf16: bool,
     pub device: i32,
     pub max_batch: i32,
@@ -44,6 +46,14 @@ impl Default for HipModelParams {
     fn default() -> Self {
         Self { bf16: true, device: 0, max_batch: 8 }
     }
+}
+
+/// `model_params` with the fp16 engine (`SPT_DTYPE_F16`, ABI 14): an f16 ggml file's matrices bit
+/// for bit, f16 activations at the GEMM inputs, the bf16 engine's memory footprint.
+fn model_params_f16(p: &HipModelParams) -> sys::spt_model_params {
+    let mut mp = model_params(p);
+    mp.dtype = sys::SPT_DTYPE_F16;
+    mp
 }
 
 fn model_params(p: &HipModelParams) -> sys::spt_model_params {
@@ -143,6 +153,29 @@ impl HipWhisperEngine {
         Ok(())
     }
 
+    fn load_model_raw(&mut self, model_path: &Path, mp: sys::spt_model_params) -> Result<(), Box<dyn Error>> {
+        TranscriptionEngine::unload_model(self);
+        // the catalog's ggml-*.bin (managers/model.rs:804-847)
+        let spec = CString::new(model_path.to_string_lossy().as_bytes())?;
+        let mut err = vec![0 as c_char; 1024];
+        let mut ctx = std::ptr::null_mut();
+        // SAFETY: valid C strings and out-pointers for the duration of the call
+        let st = unsafe { sys::spt_ctx_create(spec.as_ptr(), &mp, &mut ctx, err.as_mut_ptr(), err.len()) };
+        if st != sys::SPT_OK {
+            // SAFETY: the library NUL-terminates err
+            let msg = unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned();
+            return Err(status_error("model load", st, msg));
+        }
+        self.ctx = ctx;
+        Ok(())
+    }
+
+    /// `load_model_with_params` with the fp16 engine (ABI 14, `SPT_DTYPE_F16`): the catalog's f16
+    /// files are held bit for bit, at the bf16 engine's memory footprint.  `params.bf16` is ignored.
+    pub fn load_model_f16(&mut self, model_path: &Path, params: HipModelParams) -> Result<(), Box<dyn Error>> {
+        self.load_model_raw(model_path, model_params_f16(&params))
+    }
+
     /// Several utterances in one call (each <= 30 s window is a batch row).
     pub fn transcribe_batch(
         &mut self,
@@ -177,21 +210,7 @@ impl TranscriptionEngine for HipWhisperEngine {
     type ModelParams = HipModelParams;
 
     fn load_model_with_params(&mut self, model_path: &Path, params: HipModelParams) -> Result<(), Box<dyn Error>> {
-        self.unload_model();
-        // the catalog's ggml-*.bin (managers/model.rs:804-847)
-        let spec = CString::new(model_path.to_string_lossy().as_bytes())?;
-        let mp = model_params(&params);
-        let mut err = vec![0 as c_char; 1024];
-        let mut ctx = std::ptr::null_mut();
-        // SAFETY: valid C strings and out-pointers for the duration of the call
-        let st = unsafe { sys::spt_ctx_create(spec.as_ptr(), &mp, &mut ctx, err.as_mut_ptr(), err.len()) };
-        if st != sys::SPT_OK {
-            // SAFETY: the library NUL-terminates err
-            let msg = unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned();
-            return Err(status_error("model load", st, msg));
-        }
-        self.ctx = ctx;
-        Ok(())
+        self.load_model_raw(model_path, model_params(&params))
     }
 
     fn unload_model(&mut self) {
@@ -243,8 +262,16 @@ unsafe impl Send for HipWhisperReplicas {}
 
 impl HipWhisperReplicas {
     pub fn load(model_path: &Path, params: HipModelParams, devices: &[i32]) -> Result<Self, Box<dyn Error>> {
+        Self::load_raw(model_path, model_params(&params), devices)
+    }
+
+    /// `load` with the fp16 engine on every device (ABI 14; `params.bf16` is ignored).
+    pub fn load_f16(model_path: &Path, params: HipModelParams, devices: &[i32]) -> Result<Self, Box<dyn Error>> {
+        Self::load_raw(model_path, model_params_f16(&params), devices)
+    }
+
+    fn load_raw(model_path: &Path, mp: sys::spt_model_params, devices: &[i32]) -> Result<Self, Box<dyn Error>> {
         let spec = CString::new(model_path.to_string_lossy().as_bytes())?;
-        let mp = model_params(&params);
         let mut ctxs = vec![std::ptr::null_mut(); devices.len()];
         let mut ms = 0.0f64;
         let mut err = vec![0 as c_char; 1024];

@@ -348,7 +348,7 @@ spt_status run_windows(spt_ctx* c, std::vector<Window>& win, const float* const*
 
 extern "C" {
 
-const char* spt_version(void) { return "spittle_amd 0.13.0 (gfx950, ABI 13: additive over ABI 12)"; }
+const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12)"; }
 
 const char* spt_language_code(int32_t lang_id) { return spt::lang_code(lang_id); }
 
@@ -386,7 +386,7 @@ spt_status spt_ctx_create(const char* model_spec, const spt_model_params* params
     spt_model_params mp;
     spt_default_model_params(&mp);
     if (params) mp = *params;
-    if (mp.dtype != SPT_DTYPE_F32 && mp.dtype != SPT_DTYPE_BF16) {
+    if (mp.dtype != SPT_DTYPE_F32 && mp.dtype != SPT_DTYPE_BF16 && mp.dtype != SPT_DTYPE_F16) {  // no SPT_DTYPE_I8
         set_err(err, errlen, "bad dtype");
         return SPT_ERR_INVALID_ARG;
     }
@@ -429,7 +429,7 @@ spt_status spt_ctx_create(const char* model_spec, const spt_model_params* params
     spt_ctx* c = new (std::nothrow) spt_ctx();
     if (!c) return SPT_ERR_OOM;
     try {
-        c->eng.reset(new Engine(dm, mp.dtype == SPT_DTYPE_BF16 ? spt::DT_BF16 : spt::DT_F32, mp.device,
+        c->eng.reset(new Engine(dm, mp.dtype == SPT_DTYPE_BF16 ? spt::DT_BF16 : mp.dtype == SPT_DTYPE_F16 ? spt::DT_F16 : spt::DT_F32, mp.device,
                                 mp.max_batch, seed, file.get(), (mp.flags & SPT_MODEL_WEIGHTS_EXTERNAL) != 0));
         if (file) c->vocab.reset(new spt::Vocab(file->vocab(), dm.n_vocab, spt::specials_for(dm.n_vocab)));
     } catch (const std::exception& e) {
@@ -452,7 +452,8 @@ spt_status spt_ctx_info(const spt_ctx* ctx, spt_model_info* info) {
     const spt::ModelDims& d = ctx->eng->dims();
     info->n_mels = d.n_mels; info->d = d.d; info->n_head = d.n_head; info->n_enc = d.n_enc; info->n_dec = d.n_dec;
     info->n_vocab = d.n_vocab; info->n_audio_ctx = d.n_audio_ctx; info->n_text_ctx = d.n_text_ctx;
-    info->dtype = ctx->eng->dtype() == spt::DT_BF16 ? SPT_DTYPE_BF16 : SPT_DTYPE_F32;
+    const int dt = ctx->eng->dtype();
+    info->dtype = dt == spt::DT_BF16 ? SPT_DTYPE_BF16 : dt == spt::DT_F16 ? SPT_DTYPE_F16 : SPT_DTYPE_F32;
     info->max_batch = ctx->eng->max_batch();
     info->weight_bytes = ctx->eng->weight_bytes();
     info->workspace_bytes = ctx->eng->workspace_bytes();

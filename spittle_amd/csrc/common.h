@@ -16,6 +16,7 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2v;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2v;
 
 #define SPT_LDS __attribute__((address_space(3)))
 
@@ -56,6 +57,25 @@ __device__ inline uint32_t pack_bf2(float a, float b) {
     return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
 }
 
+// f32 -> IEEE half bits on the host (weight staging, debug inputs): round-to-nearest-even,
+// subnormals kept, overflow to infinity, NaN stays NaN -- the device's (f16) conversion
+inline uint16_t f2h_bits(float f) {
+    union { uint32_t u; float f; } x;
+    x.f = f;
+    const uint32_t sign = (x.u >> 16) & 0x8000u, a = x.u & 0x7FFFFFFFu;
+    if (a >= 0x7F800000u) return (uint16_t)(sign | 0x7C00u | (a > 0x7F800000u ? 0x200u | ((a >> 13) & 0x3FFu) : 0u));
+    if (a >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 rounds to infinity
+    if (a < 0x38800000u) {                                    // below 2^-14: subnormal half (or zero)
+        if (a < 0x33000000u) return (uint16_t)sign;           // below 2^-25 rounds to zero
+        const uint32_t shift = 126u - (a >> 23);              // 14..24: mantissa (with hidden bit) >> shift
+        const uint32_t m = (a & 0x7FFFFFu) | 0x800000u;
+        const uint32_t q = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+        return (uint16_t)(sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u)));
+    }
+    const uint32_t r = a + 0xFFFu + ((a >> 13) & 1u);         // RNE on the 13 dropped bits
+    return (uint16_t)(sign | ((r - 0x38000000u) >> 13));
+}
+
 template <typename T> struct TypeTag;
 template <> struct TypeTag<float> { static constexpr int id = 0; };
 template <> struct TypeTag<bf16> { static constexpr int id = 1; };
@@ -69,6 +89,18 @@ template <typename T> __device__ inline T from_f(float v);
 template <> __device__ inline float from_f<float>(float v) { return v; }
 template <> __device__ inline bf16 from_f<bf16>(float v) { return f2bf(v); }
 template <> __device__ inline f16 from_f<f16>(float v) { return (f16)v; }  // RNE
+
+// The store into a decoder K/V cache (self: the GV_QKV_CACHE GEMV; cross: the EPI_KVSPLIT GEMM
+// epilogue).  f16 clamps to the largest finite f16 first: the decode attention needs finite cache
+// rows (engine.cpp, beam_begin), and an f16 activation overflows at 65504 where bf16 needs ~3e38.
+// bf16 and f32 are from_f, the same stores as before the f16 mode existed.  (fmaxf returns its
+// non-NaN operand, so a NaN is stored as -65504: finite too.)
+template <typename T> __device__ inline T to_cache(float v) {
+    if constexpr (TypeTag<T>::id == TypeTag<f16>::id)
+        return (f16)__builtin_fminf(__builtin_fmaxf(v, -65504.0f), 65504.0f);
+    else
+        return from_f<T>(v);
+}
 
 // GELU, tanh form (ggml / whisper.cpp): 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3),
 // evaluated as x * sigmoid(2u) = x / (1 + 2^(-2u log2 e)): one v_exp_f32 + one v_rcp_f32

@@ -18,6 +18,11 @@ template <> struct KVChunk<bf16> {
     __device__ __forceinline__ void load(const bf16* p) { v = *(const bf16x8*)p; }
     __device__ __forceinline__ float at(int e) const { return bf2f((bf16)v[e]); }
 };
+template <> struct KVChunk<f16> {
+    f16x8 v;
+    __device__ __forceinline__ void load(const f16* p) { v = *(const f16x8*)p; }
+    __device__ __forceinline__ float at(int e) const { return (float)v[e]; }
+};
 template <> struct KVChunk<float> {
     f32x4 a, b;
     __device__ __forceinline__ void load(const float* p) { a = *(const f32x4*)p; b = *(const f32x4*)(p + 4); }
@@ -28,7 +33,7 @@ template <> struct KVChunk<float> {
 // key (8 dims each, fully coalesced 16-byte sweeps of the K/V rows), online softmax in exp2
 // space; raw K/V chunks ping-pong so the next block streams in during the current one.
 // qv is pre-scaled by log2(e)/8.  Leaves (m, l, o) per query in the calling lanes.
-// keys per lane: 4 for bf16 (r1 exp10 / exp11: lower register pressure and more resident waves
+// keys per lane: 4 for bf16 and f16 (r1 exp10 / exp11: lower register pressure and more resident waves
 // beat more keys per lane for both the cross- and the self-attention step), 2 for f32 prompts.
 // PF: key blocks in the register ring (PF - 1 in flight while one is processed); the blocks are
 // processed in the same order whatever PF is, so PF changes no result bit.

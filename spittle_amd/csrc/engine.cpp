@@ -93,7 +93,8 @@ Engine::Engine(const ModelDims& dm, int dtype, int device, int max_batch, uint64
     if (dt_ == DT_F32 && dm_.d > 1024)  // LayerNorm-prologue GEMVs stage <= 16 f32 super-steps
         throw std::runtime_error("the f32 engine supports model widths up to 1024 (tiny..medium); load " +
                                  std::to_string(dm_.d) + "-wide models in bf16");
-    esz_ = dt_ == DT_BF16 ? 2 : 4;
+    if (dt_ != DT_F32 && dt_ != DT_BF16 && dt_ != DT_F16) throw std::runtime_error("unsupported engine dtype");
+    esz_ = dtype_size(dt_);  // f16 shares bf16's 2-byte layout: arena, strides and launch geometry
     cp_ = ((dm_.n_mels + 63) / 64) * 64;
     if ((3 * cp_ * esz_) % 128) cp_ = ((dm_.n_mels + 127) / 128) * 128;
     if (const char* g = getenv("SPT_DECODE_GROUPS")) n_groups_ = std::max(1, std::min(4, atoi(g)));
@@ -415,6 +416,10 @@ void Engine::load_ggml(const GgmlFile& f) {
             if (dt_ == DT_BF16) {
                 std::vector<bf16> h(lay.size());
                 for (size_t i = 0; i < lay.size(); ++i) h[i] = f2bf(lay[i]);
+                HIP_CHECK(hipMemcpy(dst, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+            } else if (dt_ == DT_F16) {  // f16 file values survive: f16 -> f32 -> f16 is exact
+                std::vector<uint16_t> h(lay.size());
+                for (size_t i = 0; i < lay.size(); ++i) h[i] = f2h_bits(lay[i]);
                 HIP_CHECK(hipMemcpy(dst, h.data(), h.size() * 2, hipMemcpyHostToDevice));
             } else {
                 HIP_CHECK(hipMemcpy(dst, lay.data(), lay.size() * 4, hipMemcpyHostToDevice));
@@ -933,7 +938,7 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
     // 80 workgroups: 15 us at a beam's 5 rows)
     const bool vw_merge = vw && R > 1;
     const int xs = vw ? (vw_merge ? 1 : 8) : mapped ? 1 : xsplit_;
-    const int ks = dt_ == DT_BF16 ? 128 : 64;
+    const int ks = esz_ == 2 ? 128 : 64;
     hipStream_t st = g.st;
     float* xc = g.dx;   // current residual rows (dec_embed / dec_finalize wrote this pass's input here)
     float* xo = g.dx2;  // the other buffer
@@ -1467,6 +1472,11 @@ void Engine::beam_begin(int B, const DecodeRequest& rq, BeamCands* out, int* lan
         }
         // finite from the start: the self-attention reads a wave's first key block before it knows
         // the position (rows past it are masked, p = 0, and must not hold NaN / Inf bit patterns)
+        // The stores keep it so.  AttnWave::process gives a masked key fmaf(0, v, o), NaN for a
+        // non-finite v.  A bf16 store overflows to Inf only near 3e38; an f16 store would at 65504, so
+        // the f16 engine's two cache stores -- the self cache (GV_QKV_CACHE GEMV) and the cross cache
+        // (EPI_KVSPLIT GEMM epilogue) -- clamp to +-65504 before the conversion (to_cache, common.h;
+        // behind if constexpr: the bf16 / f32 stores are unchanged).  No other f16 activation saturates.
         HIP_CHECK(hipMemset(kvtmp_, 0, bytes));
     }
     beam_rq_ = rq;
@@ -1579,7 +1589,8 @@ void Engine::debug_encode(const float* mel_host, float* out_host) {
         for (int c = 0; c < nm; ++c) {
             const float v = mel_host[(size_t)c * 3000 + t];
             const size_t o = (size_t)(t + 1) * cp_ + c;
-            if (esz_ == 2) ((uint16_t*)img.data())[o] = f2bf(v);
+            if (dt_ == DT_F16) ((uint16_t*)img.data())[o] = f2h_bits(v);
+            else if (esz_ == 2) ((uint16_t*)img.data())[o] = f2bf(v);
             else ((float*)img.data())[o] = v;
         }
     HIP_CHECK(hipMemcpyAsync(mel_in_, img.data(), img.size(), hipMemcpyHostToDevice, st_));

@@ -13,18 +13,22 @@
 // product O^T += V^T . P^T (CDNA4 accumulator-as-operand layout); V^T fragments
 // come from ds_read_b64_tr_b16 transposed LDS reads.
 //   bf16: v_mfma_f32_32x32x16_bf16, f32 accumulate, bf16 P.
+//   f16 : the same kernels instantiated on the element type (v_mfma_f32_32x32x16_f16, f16 P,
+//         one v_cvt_pk_f16_f32 per pair of probabilities); P <= 2^12 and the pre-scaled Q are
+//         well inside f16's range.
 //   f32 : v_mfma_f32_32x32x2_f32 (exact f32), P kept in f32 registers.
 #include "common.h"
 #include "kernels.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace spt {
 
 namespace {
 
 constexpr float kScaleLog2 = 0.125f * 1.4426950408889634f;  // (1/sqrt(64)) * log2(e)
-constexpr float kLazy = 8.0f;  // bf16 kernel: re-base the softmax only past a 2^8 growth
+constexpr float kLazy = 8.0f;  // bf16 / f16 kernels: re-base the softmax only past a 2^8 growth
 
 __device__ __forceinline__ void glds16(const void* g, SPT_LDS void* l) {
     __builtin_amdgcn_global_load_lds((const void*)g, l, 16, 0, 0);
@@ -47,18 +51,49 @@ __device__ __forceinline__ bf16x4v ds_tr16_asm(const SPT_LDS char* base) {
 
 __device__ __forceinline__ int key_of(int kt2, int r, int hf) { return 32 * kt2 + (r & 3) + 8 * (r >> 2) + 4 * hf; }
 
-// -------------------------------------------------------------------- bf16
-__global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16* __restrict__ qkv, int T, int H,
-                                                           bf16* __restrict__ out) {
+// ---- element-type pieces of the 16-bit kernels (ET = bf16 or f16).  Fragments are carried as bf16x8
+// (eight 16-bit patterns) whatever ET is: the global / LDS loads, the glds16 staging and the
+// ds_read_b64_tr_b16 transposed reads move bits; only these four know the number format.
+template <typename ET>
+__device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c) {
+    if constexpr (std::is_same<ET, f16>::value)
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+// two probabilities -> one dword of the P^T fragment: one v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 (RNE)
+template <typename ET>
+__device__ __forceinline__ uint32_t pack_p(f32x2 pv) {
+    if constexpr (std::is_same<ET, f16>::value) return __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, f16x2v));
+    else return __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+}
+template <typename ET>
+__device__ __forceinline__ uint32_t pack_out(float a, float b) {
+    if constexpr (std::is_same<ET, f16>::value) return pack_p<f16>(f32x2{a, b});
+    else return pack_bf2(a, b);
+}
+// a Q element pre-scaled by log2(e) / 8 and rounded back to ET (SUM == 4: scores in log2 units)
+template <typename ET>
+__device__ __forceinline__ short scale_q(short q) {
+    if constexpr (std::is_same<ET, f16>::value)
+        return __builtin_bit_cast(short, (f16)((float)__builtin_bit_cast(f16, q) * kScaleLog2));
+    else
+        return (short)f2bf(bf2f((bf16)q) * kScaleLog2);
+}
+
+// -------------------------------------------------------------------- bf16 / f16
+template <typename ET = bf16>
+__global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const ET* __restrict__ qkv, int T, int H,
+                                                           ET* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) char smem[2 * 2 * 64 * 128];  // [buf][K|V][64 keys][128 B]
     const int d = H * 64, ld = 3 * d;
     const int qt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int l32 = lane & 31, hf = lane >> 5;
-    const bf16* base = qkv + (size_t)b * T * ld;
+    const ET* base = qkv + (size_t)b * T * ld;
 
     const int q_abs = qt * 128 + wid * 32 + l32;
-    const bf16* qp = base + (size_t)min(q_abs, T - 1) * ld + h * 64;
+    const ET* qp = base + (size_t)min(q_abs, T - 1) * ld + h * 64;
     bf16x8 qf[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) qf[s] = *(const bf16x8*)(qp + 16 * s + 8 * hf);
@@ -72,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16* __restric
             const int p = wid * 2 + i;
             const int rt = 8 * p + prow;
             const int key = min(kt * 64 + rt, T - 1);
-            const bf16* kr = base + (size_t)key * ld + d + h * 64;
+            const ET* kr = base + (size_t)key * ld + d + h * 64;
             glds16(kr + 8 * (pch ^ (rt & 7)), lds_k(buf) + p * 1024);
             glds16(kr + d + 8 * pch, lds_v(buf) + p * 1024);
         }
@@ -102,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16* __restric
             for (int st = 0; st < 4; ++st) {
                 const int c = 2 * st + hf;
                 const bf16x8 a = *(const SPT_LDS bf16x8*)(lk + row * 128 + ((c ^ (row & 7)) << 4));
-                s[kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qf[st], s[kt2], 0, 0, 0);
+                s[kt2] = mfma32<ET>(a, qf[st], s[kt2]);
             }
         }
         if (kt * 64 + 64 > T) {
@@ -146,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16* __restric
                 const f32x2 t = __builtin_elementwise_fma(sv, sc2, mc2);
                 const f32x2 pv = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
                 ls2 += pv;
-                pu[kt2][r >> 3].w[(r & 7) >> 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+                pu[kt2][r >> 3].w[(r & 7) >> 1] = pack_p<ET>(pv);
             }
         const float lsum = ls2[0] + ls2[1];
         bf16x8 pf[2][2];
@@ -172,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16* __restric
                     bf16x8 va;
                     va[0] = lo[0]; va[1] = lo[1]; va[2] = lo[2]; va[3] = lo[3];
                     va[4] = hi[0]; va[5] = hi[1]; va[6] = hi[2]; va[7] = hi[3];
-                    o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pf[kt2][sp], o[dt], 0, 0, 0);
+                    o[dt] = mfma32<ET>(va, pf[kt2][sp], o[dt]);
                 }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -181,14 +216,14 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_kernel(const bf16* __restric
     const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     const float inv = 1.0f / l_tot;
     if (q_abs < T) {
-        bf16* orow = out + ((size_t)b * T + q_abs) * d + h * 64;
+        ET* orow = out + ((size_t)b * T + q_abs) * d + h * 64;
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int gg = 0; gg < 4; ++gg) {
                 const int dd = 32 * dt + 8 * gg + 4 * hf;
-                *(uint2*)(orow + dd) = make_uint2(pack_bf2(o[dt][4 * gg + 0] * inv, o[dt][4 * gg + 1] * inv),
-                                                  pack_bf2(o[dt][4 * gg + 2] * inv, o[dt][4 * gg + 3] * inv));
+                *(uint2*)(orow + dd) = make_uint2(pack_out<ET>(o[dt][4 * gg + 0] * inv, o[dt][4 * gg + 1] * inv),
+                                                  pack_out<ET>(o[dt][4 * gg + 2] * inv, o[dt][4 * gg + 3] * inv));
             }
     }
 }
@@ -215,29 +250,29 @@ __device__ __forceinline__ int vswz(int r) { return (SW & 2) ? ((r & 2) << 1) : 
 // per wave, lane-linear: conflict-free ds_read_b128) and are re-read at the start of every tile.
 // Held in registers for the whole kernel they pushed it past 256 VGPRs at two waves per SIMD: 16
 // spilled, and the loop reloaded K/V stage addresses and Q pieces from scratch on every tile (r5).
-template <int SUM, int SW = 1, bool QL = false>  // row sums: 0 packed f32 VALU, 1 scalar f32 VALU, 2 an MFMA with a ones operand
-__global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __restrict__ qkv, int T, int H,
-                                                               bf16* __restrict__ out, int fulldma) {
+template <int SUM, int SW = 1, bool QL = false, typename ET = bf16>  // row sums: 0 packed f32 VALU, 1 scalar f32 VALU, 2 an MFMA with a ones operand
+__global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const ET* __restrict__ qkv, int T, int H,
+                                                               ET* __restrict__ out, int fulldma) {
     // [buf][K|V][64 keys][128 B] (+ QL: [wave][qb * 4 + s][lane] x 16 B)
     __shared__ __attribute__((aligned(16))) char smem[2 * 2 * 64 * 128 + (QL ? 4 * 8 * 64 * 16 : 0)];
     const int d = H * 64, ld = 3 * d;
     const int qt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int l32 = lane & 31, hf = lane >> 5;
-    const bf16* base = qkv + (size_t)b * T * ld;
+    const ET* base = qkv + (size_t)b * T * ld;
 
     bf16x8 qf[2][4];
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
         const int q_abs = qt * 256 + wid * 64 + 32 * qb + l32;
-        const bf16* qp = base + (size_t)min(q_abs, T - 1) * ld + h * 64;
+        const ET* qp = base + (size_t)min(q_abs, T - 1) * ld + h * 64;
 #pragma unroll
         for (int s = 0; s < 4; ++s) qf[qb][s] = *(const bf16x8*)(qp + 16 * s + 8 * hf);
         if constexpr (SUM == 4) {  // scores come out of the MFMA in log2 units: s = (q * c) . k
 #pragma unroll
             for (int s = 0; s < 4; ++s)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) qf[qb][s][e] = (short)f2bf(bf2f((bf16)qf[qb][s][e]) * kScaleLog2);
+                for (int e = 0; e < 8; ++e) qf[qb][s][e] = scale_q<ET>(qf[qb][s][e]);
         }
     }
     SPT_LDS bf16x8* qlds = (SPT_LDS bf16x8*)(smem + 2 * 2 * 64 * 128) + wid * 8 * 64;
@@ -257,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
             const int p = wid * 2 + i;
             const int rt = 8 * p + prow;
             const int key = min(kt * 64 + rt, T - 1);
-            const bf16* kr = base + (size_t)key * ld + d + h * 64;
+            const ET* kr = base + (size_t)key * ld + d + h * 64;
             glds16(kr + 8 * (pch ^ kswz<SW>(rt)), lds_k(buf) + p * 1024);
             glds16(kr + d + 8 * (pch ^ vswz<SW>(rt)), lds_v(buf) + p * 1024);
         }
@@ -282,7 +317,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
     f32x16 o[2][2], lacc[2];
     bf16x8 ones;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) ones[e] = (short)0x3F80;  // bf16 1.0
+    for (int e = 0; e < 8; ++e) ones[e] = std::is_same<ET, f16>::value ? (short)0x3C00 : (short)0x3F80;  // 1.0
 #pragma unroll
     for (int i = 0; i < 16; ++i) { lacc[0][i] = 0.f; lacc[1][i] = 0.f; }
 #pragma unroll
@@ -331,8 +366,8 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
             for (int st = 0; st < 4; ++st) {
                 const int c = 2 * st + hf;
                 const bf16x8 a = *(const SPT_LDS bf16x8*)(lk + row * 128 + ((c ^ kswz<SW>(row)) << 4));
-                s[0][kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qfrag(0, st), st == 0 ? cinit[0] : s[0][kt2], 0, 0, 0);
-                s[1][kt2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, qfrag(1, st), st == 0 ? cinit[1] : s[1][kt2], 0, 0, 0);
+                s[0][kt2] = mfma32<ET>(a, qfrag(0, st), st == 0 ? cinit[0] : s[0][kt2]);
+                s[1][kt2] = mfma32<ET>(a, qfrag(1, st), st == 0 ? cinit[1] : s[1][kt2]);
             }
         }
         if (kt * 64 + 64 > T) {
@@ -363,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
                             l0 += p0;
                             l1 += p1;
                             const f32x2 pv = {p0, p1};
-                            pu[kt2][r >> 3].w[(r & 7) >> 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+                            pu[kt2][r >> 3].w[(r & 7) >> 1] = pack_p<ET>(pv);
                         }
                     return l0 + l1;
                 };
@@ -378,7 +413,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
                             l0 += p0;
                             l1 += p1;
                             const f32x2 pv = {p0, p1};
-                            pu[kt2][r >> 3].w[(r & 7) >> 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+                            pu[kt2][r >> 3].w[(r & 7) >> 1] = pack_p<ET>(pv);
                         }
                     return l0 + l1;
                 };
@@ -431,7 +466,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
                             const f32x2 t = __builtin_elementwise_fma(sv, sc2, mc2);
                             const f32x2 pv = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
                             ls2 += pv;
-                            pu[kt2][r >> 3].w[(r & 7) >> 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+                            pu[kt2][r >> 3].w[(r & 7) >> 1] = pack_p<ET>(pv);
                         }
                     return ls2[0] + ls2[1];
                 };
@@ -488,7 +523,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
                         const f32x2 t = __builtin_elementwise_fma(sv, sc2, mc2);
                         const f32x2 pv = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
                         ls2 += pv;
-                        pu[kt2][r >> 3].w[(r & 7) >> 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+                        pu[kt2][r >> 3].w[(r & 7) >> 1] = pack_p<ET>(pv);
                     }
                 lsum[qb] += ls2[0] + ls2[1];
             } else {  // scalar f32 FMA (packed f32 VALU costs extra issue cycles beside MFMAs)
@@ -501,7 +536,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
                         const float p1 = __builtin_amdgcn_exp2f(fmaf(s[qb][kt2][r + 1], kScaleLog2, -mc));
                         if constexpr (SUM == 1) ls += p0 + p1;
                         const f32x2 pv = {p0, p1};
-                        pu[kt2][r >> 3].w[(r & 7) >> 1] = __builtin_bit_cast(uint32_t, __builtin_convertvector(pv, bf16x2v));
+                        pu[kt2][r >> 3].w[(r & 7) >> 1] = pack_p<ET>(pv);
                     }
                 if constexpr (SUM == 1) lsum[qb] += ls;
             }
@@ -542,8 +577,8 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
 #pragma unroll
                     for (int sp = 0; sp < 2; ++sp) {
                         const bf16x8 va = __builtin_shufflevector(lo[kt2][sp], hi[kt2][sp], 0, 1, 2, 3, 4, 5, 6, 7);
-                        o[0][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pf[0][kt2][sp], o[0][dt], 0, 0, 0);
-                        o[1][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pf[1][kt2][sp], o[1][dt], 0, 0, 0);
+                        o[0][dt] = mfma32<ET>(va, pf[0][kt2][sp], o[0][dt]);
+                        o[1][dt] = mfma32<ET>(va, pf[1][kt2][sp], o[1][dt]);
                     }
             }
         } else
@@ -563,8 +598,8 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
                     // a concatenation, not eight element inserts (which cost ~120 shift / or /
                     // and VALU per tile beside 32 MFMAs, r4)
                     const bf16x8 va = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                    o[0][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pf[0][kt2][sp], o[0][dt], 0, 0, 0);
-                    o[1][dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va, pf[1][kt2][sp], o[1][dt], 0, 0, 0);
+                    o[0][dt] = mfma32<ET>(va, pf[0][kt2][sp], o[0][dt]);
+                    o[1][dt] = mfma32<ET>(va, pf[1][kt2][sp], o[1][dt]);
                 }
         }
         // row sums of the (bf16) probabilities: ones . P^T
@@ -573,8 +608,8 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
         for (int kt2 = 0; kt2 < 2; ++kt2)
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) {
-                lacc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pf[0][kt2][sp], lacc[0], 0, 0, 0);
-                lacc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pf[1][kt2][sp], lacc[1], 0, 0, 0);
+                lacc[0] = mfma32<ET>(ones, pf[0][kt2][sp], lacc[0]);
+                lacc[1] = mfma32<ET>(ones, pf[1][kt2][sp], lacc[1]);
             }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -588,14 +623,14 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_q64_kernel(const bf16* __res
         const float inv = 1.0f / (SUM == 2 ? lacc[qb][0] : lsum[qb] + __shfl_xor(lsum[qb], 32, 64));
         const int q_abs = qt * 256 + wid * 64 + 32 * qb + l32;
         if (q_abs < T) {
-            bf16* orow = out + ((size_t)b * T + q_abs) * d + h * 64;
+            ET* orow = out + ((size_t)b * T + q_abs) * d + h * 64;
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
                 for (int gg = 0; gg < 4; ++gg) {
                     const int dd = 32 * dt + 8 * gg + 4 * hf;
-                    *(uint2*)(orow + dd) = make_uint2(pack_bf2(o[qb][dt][4 * gg + 0] * inv, o[qb][dt][4 * gg + 1] * inv),
-                                                      pack_bf2(o[qb][dt][4 * gg + 2] * inv, o[qb][dt][4 * gg + 3] * inv));
+                    *(uint2*)(orow + dd) = make_uint2(pack_out<ET>(o[qb][dt][4 * gg + 0] * inv, o[qb][dt][4 * gg + 1] * inv),
+                                                      pack_out<ET>(o[qb][dt][4 * gg + 2] * inv, o[qb][dt][4 * gg + 3] * inv));
                 }
         }
     }
@@ -750,9 +785,18 @@ void enc_attention(int dtype, const void* qkv, int B, int T, int H, void* out, h
         else hipLaunchKernelGGL((attn_bf16_q64_kernel<0, 3>), g, dim3(256), 0, st, (const bf16*)qkv, T, H, (bf16*)out, fulldma);
         return;
     }
+    // f16: the production variant (SUM = 4, SWZ = 3, Q in LDS) only; the SUM / SWZ / QL switches above
+    // are the bf16 kernel's A/B experiments
+    if (dtype == DT_F16 && !q32) {
+        hipLaunchKernelGGL((attn_bf16_q64_kernel<4, 3, true, f16>), dim3(cdiv(T, 256), H, B), dim3(256), 0, st,
+                           (const f16*)qkv, T, H, (f16*)out, fulldma);
+        return;
+    }
     dim3 grid(cdiv(T, 128), H, B);
     if (dtype == DT_BF16)
-        hipLaunchKernelGGL(attn_bf16_kernel, grid, dim3(256), 0, st, (const bf16*)qkv, T, H, (bf16*)out);
+        hipLaunchKernelGGL(attn_bf16_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)qkv, T, H, (bf16*)out);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(attn_bf16_kernel<f16>, grid, dim3(256), 0, st, (const f16*)qkv, T, H, (f16*)out);
     else
         hipLaunchKernelGGL(attn_f32_kernel, grid, dim3(256), 0, st, (const float*)qkv, T, H, (float*)out);
 }

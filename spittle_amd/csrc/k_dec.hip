@@ -8,7 +8,7 @@
 // are "GEMV" kernels: a workgroup owns 16 x CT output columns; its 4 waves split
 // the column tiles and K; each lane streams 64 contiguous bytes of one weight
 // row per step straight into registers (two steps in flight, no LDS round trip)
-// and the rows x 16 tile is an MFMA (16x16x32 bf16 / 16x16x4 f32) with the
+// and the rows x 16 tile is an MFMA (16x16x32 bf16 or f16 / 16x16x4 f32) with the
 // activations as the A operand.  A fused pre-LayerNorm is computed once per
 // workgroup into a bank-padded LDS image that the MFMA A fragments read;
 // bias / GELU / residual / KV-cache append are fused epilogues.
@@ -24,6 +24,7 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #ifndef SPT_STAMP
 #define SPT_STAMP 0
@@ -63,6 +64,10 @@ template <typename T> struct GV;
 template <> struct GV<bf16> {
     static constexpr int KS = 128;  // K per super-step: 4 lane groups x 32 elements
     typedef bf16x8 frag;
+};
+template <> struct GV<f16> {
+    static constexpr int KS = 128;  // bf16's geometry: 4 lane groups x 32 elements
+    typedef f16x8 frag;
 };
 template <> struct GV<float> {
     static constexpr int KS = 64;   // 4 lane groups x 16 elements
@@ -360,7 +365,11 @@ __global__ __launch_bounds__(64 * NWV) void gemv_kernel(GemvArgs a) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) af[i] = frag{};
                 }
-                if constexpr (sizeof(T) == 2) {
+                if constexpr (std::is_same<T, f16>::value) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], w[j][i], acc[g], 0, 0, 0);
+                } else if constexpr (sizeof(T) == 2) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
                         acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], w[j][i], acc[g], 0, 0, 0);
@@ -455,7 +464,7 @@ __global__ __launch_bounds__(64 * NWV) void gemv_kernel(GemvArgs a) {
                     const int bb = row / a.Tq, t = row - bb * a.Tq;
                     const int pos = st_pre + t;
                     const size_t off = ((((size_t)part * a.cache_B + bb) * a.cache_H + hh) * a.cache_ctx + pos) * 64 + e;
-                    ((T*)a.cache)[off] = from_f<T>(y);
+                    ((T*)a.cache)[off] = to_cache<T>(y);
                 }
             }
         }
@@ -879,11 +888,12 @@ __global__ void reset_kernel(DecState* ds, unsigned* arrive) {
 
 void gemv_prepare(int dtype) {
     if (dtype == DT_BF16) gemv_attr_modes<bf16>();
+    else if (dtype == DT_F16) gemv_attr_modes<f16>();
     else gemv_attr_modes<float>();
 }
 
 int gemv_max_image_rows(int dtype, int K) {
-    const int esz = dtype == DT_BF16 ? 2 : 4;
+    const int esz = dtype_size(dtype);
     int r = 64;
     while (r > 1 && gv_img_bytes(r, K, esz) > GV_LDS_BYTES) --r;
     return r;
@@ -891,13 +901,13 @@ int gemv_max_image_rows(int dtype, int K) {
 
 void gemv(int dtype, int mode, int asrc, const GemvArgs& a_in, hipStream_t st) {
     if (a_in.R > 64 || a_in.R <= 0) throw std::runtime_error("gemv: rows must be in 1..64");
-    const int ks = dtype == DT_BF16 ? 128 : 64;
+    const int ks = dtype_size(dtype) == 2 ? 128 : 64;
     if (a_in.K % ks) throw std::runtime_error("gemv: K alignment");
     GemvArgs a = a_in;
     a.ksplit = std::max(1, a.ksplit);
     if (a.ksplit > 1 && mode != GV_PARTIAL) throw std::runtime_error("gemv: K split needs partial outputs");
     if (a.ksplit > a.K / ks) throw std::runtime_error("gemv: K split exceeds the super-steps");
-    const int esz = dtype == DT_BF16 ? 2 : 4;
+    const int esz = dtype_size(dtype);
     if (asrc != A_DIRECT && gv_img_bytes(a.R, a.K, esz) > GV_LDS_BYTES)
         throw std::runtime_error("gemv: A image exceeds the LDS budget");
     if (asrc == A_LN && (a.K > 1536 || !a.ln_w || !a.ln_b))
@@ -914,6 +924,7 @@ void gemv(int dtype, int mode, int asrc, const GemvArgs& a_in, hipStream_t st) {
 #define SPT_GV(M, S)                                                      \
     if (mode == M && code == S) {                                         \
         if (dtype == DT_BF16) gemv_launch<bf16, M, S>(a, st);             \
+        else if (dtype == DT_F16) gemv_launch<f16, M, S>(a, st);          \
         else gemv_launch<float, M, S>(a, st);                             \
         return;                                                           \
     }
@@ -926,6 +937,8 @@ void dec_embed(int dtype, const int* tok, int R, int Tq, int d, const void* tok_
                const DecState* ds, float* x, hipStream_t st) {
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(embed_kernel<bf16>, dim3(R), dim3(256), 0, st, tok, Tq, d, (const bf16*)tok_emb, pos_emb, ds, x);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(embed_kernel<f16>, dim3(R), dim3(256), 0, st, tok, Tq, d, (const f16*)tok_emb, pos_emb, ds, x);
     else
         hipLaunchKernelGGL(embed_kernel<float>, dim3(R), dim3(256), 0, st, tok, Tq, d, (const float*)tok_emb, pos_emb, ds, x);
 }
@@ -938,6 +951,8 @@ void dec_self_attn(int dtype, const void* q, const void* cache, int B, int H, in
     hipLaunchKernelGGL((self_attn_kernel<T, NQ>), grid, blk, 0, st, (const T*)q, H * 64, (const T*)cache, B, H, ctx, Tq, ds, (T*)out)
     if (dtype == DT_BF16) {
         if (Tq == 1) SPT_SA(bf16, 1); else SPT_SA(bf16, 4);
+    } else if (dtype == DT_F16) {
+        if (Tq == 1) SPT_SA(f16, 1); else SPT_SA(f16, 4);
     } else {
         if (Tq == 1) SPT_SA(float, 1); else SPT_SA(float, 4);
     }
@@ -961,11 +976,11 @@ void dec_cross_attn(int dtype, const void* q, const void* kv, int B, int B_layou
         throw std::runtime_error("dec_cross_attn: a layer's cross K/V exceeds 2^31 elements");
     const int nq = share * Tq;
     // queries per workgroup: 1 or 4 as without a window map; a decode step of several rows per
-    // window takes 5 (bf16: beam 5 / best_of 5 in one workgroup; 8 would spill) or 4 (f32) of
+    // window takes 5 (bf16 / f16: beam 5 / best_of 5 in one workgroup; 8 would spill) or 4 (f32) of
     // them.  Every variant gives each lane the
     // same keys as the one-row kernel of the same Tq (NI: keys per lane), so a row's result is
     // bitwise the same whether or not its window is shared.
-    const int NQ = nq == 1 ? 1 : Tq > 1 ? 4 : (dtype == DT_BF16 ? 5 : 4);
+    const int NQ = nq == 1 ? 1 : Tq > 1 ? 4 : (dtype_size(dtype) == 2 ? 5 : 4);
     if (splits > 1 && nq > NQ) throw std::runtime_error("dec_cross_attn: key chunks need one query chunk per window");
     const dim3 grid((B / share) * H, splits > 1 ? splits : cdiv(nq, NQ)), blk(64 * AW);
 #define SPT_XA(T, NQ_, SP, NI, ...)                                                                             \
@@ -983,6 +998,7 @@ void dec_cross_attn(int dtype, const void* q, const void* kv, int B, int B_layou
     else if (NQ == 4) { if (splits > 1) SPT_XA(T, 4, true, 4); else SPT_XA(T, 4, false, 4); } \
     else { if (splits > 1) SPT_XA(T, 5, true, 4); else SPT_XA(T, 5, false, 4); }
     if (dtype == DT_BF16) { SPT_XA_T(bf16); }
+    else if (dtype == DT_F16) { SPT_XA_T(f16); }
     else { SPT_XA_T(float); }
 #undef SPT_XA_T
 #undef SPT_XA
@@ -1001,7 +1017,7 @@ void dec_cross_attn_vw(int dtype, const void* q, const void* kv, int B, int B_la
     // the same query chunks and keys per lane as dec_cross_attn (bitwise the same partials); per_query
     // (one-token steps): one query per workgroup, the window's K/V re-read per query from L2 -- the
     // same 4 keys per lane as the shared kernels' NIX = 4, so still bitwise the same partials
-    const int NQ = (nq == 1 || (per_query && Tq == 1)) ? 1 : Tq > 1 ? 4 : (dtype == DT_BF16 ? 5 : 4);
+    const int NQ = (nq == 1 || (per_query && Tq == 1)) ? 1 : Tq > 1 ? 4 : (dtype_size(dtype) == 2 ? 5 : 4);
     const dim3 grid((B / share) * H, AW, cdiv(nq, NQ)), blk(64);
 #define SPT_XV(T, NQ_, NI, PF)                                                                               \
     hipLaunchKernelGGL((cross_attn_vw_kernel<T, NQ_, NI, PF>), grid, blk, 0, st, (const T*)q, (const T*)kv,      \
@@ -1016,6 +1032,7 @@ void dec_cross_attn_vw(int dtype, const void* q, const void* kv, int B, int B_la
     else if (NQ == 4) SPT_XV(T, 4, 4, 2);                   \
     else { SPT_XV_PF(T, 5, 4) }
     if (dtype == DT_BF16) { SPT_XV_T(bf16); }
+    else if (dtype == DT_F16) { SPT_XV_T(f16); }
     else { SPT_XV_T(float); }
 #undef SPT_XV_T
 #undef SPT_XV_PF
@@ -1026,12 +1043,14 @@ void dec_cross_attn_vw(int dtype, const void* q, const void* kv, int B, int B_la
 void dec_attn_part_merge(int dtype, const float* part, int R, int H, void* out, hipStream_t st) {
     if (R < 1 || H < 1 || !part || !out) throw std::runtime_error("dec_attn_part_merge: empty or missing buffers");
     if (dtype == DT_BF16) hipLaunchKernelGGL(attn_part_merge_kernel<bf16>, dim3(R * H), dim3(64), 0, st, part, H, (bf16*)out);
+    else if (dtype == DT_F16) hipLaunchKernelGGL(attn_part_merge_kernel<f16>, dim3(R * H), dim3(64), 0, st, part, H, (f16*)out);
     else hipLaunchKernelGGL(attn_part_merge_kernel<float>, dim3(R * H), dim3(64), 0, st, part, H, (float*)out);
     SPT_LAUNCH_CHECK();
 }
 
 void dec_finalize(int dtype, const FinalizeArgs& a, int B, hipStream_t st) {
     if (dtype == DT_BF16) hipLaunchKernelGGL(finalize_kernel<bf16>, dim3(B), dim3(FIN_T), 0, st, a);
+    else if (dtype == DT_F16) hipLaunchKernelGGL(finalize_kernel<f16>, dim3(B), dim3(FIN_T), 0, st, a);
     else hipLaunchKernelGGL(finalize_kernel<float>, dim3(B), dim3(FIN_T), 0, st, a);
 }
 

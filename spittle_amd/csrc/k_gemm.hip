@@ -105,7 +105,7 @@ __device__ __forceinline__ void epi_store(const GemmArgs& g, int bz, int row, co
         ((float*)g.C + (size_t)bz * g.sC)[(size_t)row * g.ldc + e.col] = y + g.alpha * v;
     } else if constexpr (EPI == EPI_KVSPLIT) {
         const int bb = row / g.kv_T, t = row - bb * g.kv_T;
-        ((T*)g.C)[kv_offset(e.l, e.kvi, bb, e.h, t, e.el, g.kv_B, g.kv_H, g.kv_T)] = from_f<T>(v);
+        ((T*)g.C)[kv_offset(e.l, e.kvi, bb, e.h, t, e.el, g.kv_B, g.kv_H, g.kv_T)] = to_cache<T>(v);
     }
 }
 
@@ -535,6 +535,7 @@ __global__ __launch_bounds__(512, 1) void gemm256_kernel(GemmArgs g) {
                     if constexpr (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.0f);
                     if constexpr (EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_F32) v *= g.alpha;
                     if constexpr (F32OUT) *(float*)(wreg + rl * RS + cl * 4) = v;
+                    else if constexpr (F16 && EPI == EPI_KVSPLIT) *(f16*)(wreg + rl * RS + cl * 2) = to_cache<f16>(v);  // clamped
                     else if constexpr (F16) *(f16*)(wreg + rl * RS + cl * 2) = (f16)v;
                     else *(bf16*)(wreg + rl * RS + cl * 2) = f2bf(v);
                 }

@@ -10,6 +10,8 @@
 #include "kernels.h"
 #include "ggml_quant.h"
 
+#include <type_traits>
+
 namespace spt {
 
 namespace {
@@ -105,6 +107,8 @@ void gen_conv_weights(int store_dtype, void* dst, int N, int C, int Cp, uint64_t
     const int64_t n = (int64_t)N * 3 * Cp;
     if (store_dtype == DT_BF16)
         hipLaunchKernelGGL(gen_conv_kernel<bf16>, dim3(grid_for(n)), dim3(256), 0, st, (bf16*)dst, N, C, Cp, seed, tid, scale);
+    else if (store_dtype == DT_F16)
+        hipLaunchKernelGGL(gen_conv_kernel<f16>, dim3(grid_for(n)), dim3(256), 0, st, (f16*)dst, N, C, Cp, seed, tid, scale);
     else
         hipLaunchKernelGGL(gen_conv_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, (float*)dst, N, C, Cp, seed, tid, scale);
 }
@@ -145,13 +149,21 @@ void stream_read(const void* p, int64_t bytes, unsigned* sink, int grid, int tpb
 // Model loading (ggml_file.h): the raw ggml blocks are copied to the device as they lie in the
 // file and expanded here into the engine's storage type, one thread per block (per element for
 // f32 / f16), by the routine the host shares (ggml_quant.h); values are f32, then rounded once
-// to bf16 (RNE) for a bf16 engine.
+// to bf16 (RNE) for a bf16 engine or to f16 (RNE, subnormals kept) for an f16 engine.  An f16 engine
+// copies GQ_F16 tensors bit for bit (no trip through f32: NaN payloads included).
 namespace {
 template <typename T>
 __global__ __launch_bounds__(256) void dequant_kernel(int type, const uint8_t* __restrict__ src, int64_t n,
                                                       T* __restrict__ dst) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     if (type == GQ_F32 || type == GQ_F16) {
+        if constexpr (std::is_same<T, f16>::value) {
+            if (type == GQ_F16) {
+                for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+                    ((uint16_t*)dst)[i] = (uint16_t)(src[2 * i] | (src[2 * i + 1] << 8));
+                return;
+            }
+        }
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
             dst[i] = from_f<T>(type == GQ_F32 ? ((const float*)src)[i] : gq_half(src + 2 * i));
         return;
@@ -172,6 +184,8 @@ void ggml_dequant(int type, const void* src, int64_t n, int out_dtype, void* dst
     const int g = grid_for(n / blck);
     if (out_dtype == DT_BF16)
         hipLaunchKernelGGL(dequant_kernel<bf16>, dim3(g), dim3(256), 0, st, type, (const uint8_t*)src, n, (bf16*)dst);
+    else if (out_dtype == DT_F16)
+        hipLaunchKernelGGL(dequant_kernel<f16>, dim3(g), dim3(256), 0, st, type, (const uint8_t*)src, n, (f16*)dst);
     else
         hipLaunchKernelGGL(dequant_kernel<float>, dim3(g), dim3(256), 0, st, type, (const uint8_t*)src, n, (float*)dst);
     SPT_LAUNCH_CHECK();

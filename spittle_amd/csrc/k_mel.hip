@@ -217,6 +217,9 @@ void mel_norm(int dtype, const float* mel_raw, const unsigned* mel_max, MelUtts 
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(mel_norm_kernel<bf16>, grid, dim3(128), 0, st, mel_raw, mel_max, u, win_utt, win_seek,
                            n_mels, Cp, (bf16*)mel_in, dbg);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(mel_norm_kernel<f16>, grid, dim3(128), 0, st, mel_raw, mel_max, u, win_utt, win_seek,
+                           n_mels, Cp, (f16*)mel_in, dbg);
     else
         hipLaunchKernelGGL(mel_norm_kernel<float>, grid, dim3(128), 0, st, mel_raw, mel_max, u, win_utt, win_seek,
                            n_mels, Cp, (float*)mel_in, dbg);

@@ -669,6 +669,9 @@ void dec_kv_gather(int dtype, const void* src, void* dst, const int* rows, int L
     if (dtype == DT_BF16)
         hipLaunchKernelGGL(kv_gather_kernel<bf16>, dim3(2048), dim3(256), 0, st, (const bf16*)src, (bf16*)dst, rows, L, B,
                            H, ctx, ds);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(kv_gather_kernel<f16>, dim3(2048), dim3(256), 0, st, (const f16*)src, (f16*)dst, rows, L, B,
+                           H, ctx, ds);
     else
         hipLaunchKernelGGL(kv_gather_kernel<float>, dim3(2048), dim3(256), 0, st, (const float*)src, (float*)dst, rows, L,
                            B, H, ctx, ds);
@@ -686,6 +689,7 @@ void dec_finalize_ts(int dtype, const TsArgs& a, int B, hipStream_t st) {
     if (!a.stat) throw std::runtime_error("finalize_ts: no chunk statistics (dec_ts_stats)");
     if (a.n_vocab < 1 || a.n_vocab > VJ * TW) throw std::runtime_error("finalize_ts: vocabulary above 53248 tokens");
     if (dtype == DT_BF16) hipLaunchKernelGGL(finalize_ts_kernel<bf16>, dim3(B), dim3(TW), 0, st, a);
+    else if (dtype == DT_F16) hipLaunchKernelGGL(finalize_ts_kernel<f16>, dim3(B), dim3(TW), 0, st, a);
     else hipLaunchKernelGGL(finalize_ts_kernel<float>, dim3(B), dim3(TW), 0, st, a);
     SPT_LAUNCH_CHECK();
 }

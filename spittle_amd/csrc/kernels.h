@@ -7,9 +7,12 @@
 
 namespace spt {
 
-// DT_F16: the Parakeet encoder only; DT_I8: the Parakeet encoder's int8 mode (f32 activations,
-// int8 GEMM operands: k_pk_i8.hip), no kernel outside it takes it
+// DT_F16: the Parakeet encoder and the Whisper engine's fp16 mode; DT_I8: the Parakeet
+// encoder's int8 mode (f32 activations, int8 GEMM operands: k_pk_i8.hip), no kernel outside it takes it
 enum { DT_F32 = 0, DT_BF16 = 1, DT_F16 = 2, DT_I8 = 3 };
+// bytes per stored element of a Whisper engine dtype (DT_F32 / DT_BF16 / DT_F16): every launch
+// geometry that depends only on the element size takes it from here, so f16 runs bf16's shapes
+inline int dtype_size(int dtype) { return dtype == DT_F32 ? 4 : 2; }
 
 // ------------------------------------------------------------------ GEMM (k_gemm.hip)
 // Cross-attention K/V cache layout: per decoder layer [ceil(T/32)][B][H][2][32][64] -- 32-key
@@ -53,7 +56,7 @@ void gemm_nt_variant(int dtype, int epi, const GemmArgs& g, int batch, int varia
 
 // ------------------------------------------------------------------ weights (k_init.hip)
 enum { WK_MAT = 0, WK_BIAS = 1, WK_LNW = 2, WK_LNB = 3, WK_TOK = 4, WK_DPOS = 5 };
-// dst[i] = value(seed, tid, i) for i in [0, n); stored as f32 or bf16 (RNE)
+// dst[i] = value(seed, tid, i) for i in [0, n); stored as f32, bf16 or f16 (RNE)
 void gen_weights(int store_dtype, void* dst, int64_t n, uint64_t seed, uint32_t tid, int kind,
                  int scale_exp, hipStream_t st);
 // canonical conv weight [N][C][3] -> device [N][3][Cp] (zero for c >= C)
@@ -61,7 +64,8 @@ void gen_conv_weights(int store_dtype, void* dst, int N, int C, int Cp, uint64_t
                       int scale_exp, hipStream_t st);
 void fill_f32(float* dst, int64_t n, float v, hipStream_t st);
 // read `bytes` of p once (measurement: cold caches before a probed launch)
-// ggml tensor bytes on the device -> engine storage (out_dtype DT_F32 / DT_BF16); type is the
+// ggml tensor bytes on the device -> engine storage (out_dtype DT_F32 / DT_BF16 / DT_F16; f16 tensors
+// reach an f16 engine bit for bit, everything else is dequantised in f32 and rounded once); type is the
 // ggml type id (ggml_quant.h GQ_*), n a multiple of the type's block
 void ggml_dequant(int type, const void* src, int64_t n, int out_dtype, void* dst, hipStream_t st);
 void cache_flush(const void* p, int64_t bytes, unsigned* sink, hipStream_t st);

@@ -29,7 +29,7 @@ static void* dalloc(size_t bytes) {
     return p;
 }
 static void* drand(size_t n, int dt, uint32_t tid, int e) {
-    void* p = dalloc(n * (dt == DT_BF16 ? 2 : 4));
+    void* p = dalloc(n * (dtype_size(dt)));
     gen_weights(dt, p, (int64_t)n, 7, tid, WK_MAT, e, 0);
     return p;
 }
@@ -240,7 +240,7 @@ int main(int argc, char** argv) {
         const int N = ai(2, 1280), K = ai(3, 1280), R = ai(4, 8), mode = ai(5, 2), ln = ai(6, 0), dt = ai(7, DT_BF16),
                   ksplit = ai(8, 1), npend = ai(9, 0);
         gemv_prepare(dt);
-        const int esz = dt == DT_BF16 ? 2 : 4;
+        const int esz = dtype_size(dt);
         void* W = drand((size_t)N * K, dt, 1, -5);
         float* bias = frand(N, 2, -5);
         float* lnw = frand(K, 3, -3);
@@ -268,7 +268,7 @@ int main(int argc, char** argv) {
     }
     if (what == "attn") {  // self-attention (causal) over nkeys cached keys
         const int B = ai(2, 8), H = ai(3, 20), ctx = ai(4, 448), nk = ai(5, 132), Tq = ai(6, 1), dt = ai(7, DT_BF16);
-        const int esz = dt == DT_BF16 ? 2 : 4;
+        const int esz = dtype_size(dt);
         void* q = drand((size_t)B * Tq * H * 64, dt, 1, 0);
         void* kv = drand((size_t)2 * B * H * ctx * 64, dt, 2, 0);
         void* out = dalloc((size_t)B * Tq * H * 64 * esz);
@@ -281,7 +281,7 @@ int main(int argc, char** argv) {
     }
     if (what == "xattn") {  // cross-attention over T encoder keys of NL layers back to back (cache-cold)
         const int B = ai(2, 8), T = ai(3, 1500), S = ai(4, 1), dt = ai(5, DT_BF16), NL = 8, d = 1280, H = 20;
-        const int esz = dt == DT_BF16 ? 2 : 4;
+        const int esz = dtype_size(dt);
         void* q = drand((size_t)B * d, dt, 1, 0);
         const size_t layer = (size_t)2 * B * H * ((T + 31) / 32 * 32) * 64;
         void* kv = drand(layer * NL, dt, 2, 0);
@@ -384,7 +384,7 @@ int main(int argc, char** argv) {
         // layer2: two independent chains of batch B on two streams (can they overlap?)
         const int B = ai(2, 8), dt = ai(3, DT_BF16), xs = ai(4, 1), d = 1280, H = 20, ctx = 448, T = 1500;
         gemv_prepare(dt);
-        const int esz = dt == DT_BF16 ? 2 : 4;
+        const int esz = dtype_size(dt);
         void* wqkv = drand((size_t)3 * d * d, dt, 1, -4);
         void* wo = drand((size_t)d * d, dt, 2, -4);
         void* wq = drand((size_t)d * d, dt, 3, -4);

@@ -36,7 +36,7 @@ class TranscriptionError(RuntimeError):
 
 @dataclass
 class WhisperModelParams:
-    dtype: str = "bf16"          # "bf16" | "f32"
+    dtype: str = "bf16"          # "bf16" | "f16" | "f32" (dtype_code)
     device: int = 0
     max_batch: int = 8
     seed: int = 1234             # synthetic weights
@@ -143,6 +143,17 @@ def _take_result(rp) -> TranscriptionResult:
     return res
 
 
+_DTYPES = {"f32": L.SPT_DTYPE_F32, "bf16": L.SPT_DTYPE_BF16, "f16": L.SPT_DTYPE_F16}
+
+
+def dtype_code(dtype: str) -> int:
+    """``WhisperModelParams.dtype`` -> ``spt_model_params.dtype`` ("bf16", "f16" or "f32"; needs no device)."""
+    try:
+        return _DTYPES[dtype]
+    except KeyError:
+        raise ValueError(f"unknown Whisper engine dtype {dtype!r}: expected one of {sorted(_DTYPES)}") from None
+
+
 class WhisperEngine:
     """transcribe_rs::engines::whisper::WhisperEngine, MI355X-native."""
 
@@ -159,7 +170,7 @@ class WhisperEngine:
         self.unload_model()
         mp = L.ModelParams()
         self._lib.spt_default_model_params(C.byref(mp))
-        mp.dtype = L.SPT_DTYPE_BF16 if self.params.dtype == "bf16" else L.SPT_DTYPE_F32
+        mp.dtype = dtype_code(self.params.dtype)
         mp.device = int(self.params.device)
         mp.max_batch = int(self.params.max_batch)
         mp.seed = int(self.params.seed)
