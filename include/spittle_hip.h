@@ -536,6 +536,102 @@ spt_status spt_vad_reset(spt_vad* v, int32_t reset_model_state);
 const char* spt_vad_last_error(const spt_vad* v);
 void spt_vad_destroy(spt_vad* v);
 
+/* ================================================================================================
+ * Moonshine (additive over ABI 14, announced by SPT_HAS_MOONSHINE): the app's third local engine.
+ *
+ * Replaces transcribe_rs::engines::moonshine::MoonshineEngine as TranscriptionManager drives it
+ * through `LoadedEngine::Moonshine` (src-tauri/src/managers/transcription.rs:260-341, 444-534):
+ *
+ *   load_model_with_params(&path, MoonshineModelParams::variant(ModelVariant::Base))  -> spt_moonshine_create
+ *   transcribe_samples(audio, None)                                                   -> spt_moonshine_transcribe
+ *   unload_model() / Drop                                                             -> spt_moonshine_destroy
+ *
+ * The model is an encoder-decoder transformer over raw 16 kHz PCM (no mel): three strided 1-D
+ * convolutions with a whole-utterance GroupNorm, partial interleaved rotary positions, head dim 52
+ * (Base) or 36 (Tiny), a SiLU-gated decoder MLP, greedy decoding from <s> to </s> or to
+ * ceil(tokens_per_second * seconds) tokens.  The arithmetic is HF transformers' modeling_moonshine.py;
+ * a batch row computes what it computes alone (the B = 1 semantics the app has).  Engine dtype is
+ * fp16 only: f16 weights and GEMM inputs, f32 accumulation, residual stream, norms and softmax.
+ * Weights come from a synthetic spec or tensor by tensor, keyed by HF state-dict name.
+ * DESIGN.md §12 is the contract.
+ * ============================================================================================== */
+#define SPT_HAS_MOONSHINE 1
+
+typedef struct spt_ms_ctx spt_ms_ctx;
+
+typedef struct {
+    int32_t dtype;        /* SPT_DTYPE_F16 (default); every other dtype: SPT_ERR_UNSUPPORTED */
+    int32_t device;
+    int32_t max_batch;    /* utterances per device pass, <= 64 (default 8); longer batches run in passes */
+    int32_t max_samples;  /* the longest utterance taken: 895..3000000 (187.5 s), default 64 s = 1024000;
+                             a longer utterance: SPT_ERR_INVALID_ARG */
+    uint64_t seed;        /* synthetic weights (a ":seed=S" in the spec wins) */
+} spt_ms_model_params;
+
+typedef struct {
+    float tokens_per_second;  /* token limit = ceil(tokens_per_second * n_samples / 16000); default 6.5 */
+    int32_t max_tokens;       /* > 0: the limit itself, whatever the length (both are capped at the
+                                 context's capacity, spt_ms_model_info.ctx) */
+} spt_ms_infer_params;
+
+typedef struct {
+    char* text;            /* pieces joined: specials dropped, byte pieces to bytes, "▁" -> space, leading
+                              space stripped; "[id]" per token without a vocabulary */
+    int32_t* tokens;       /* the generated ids, </s> not included */
+    float* top1;           /* each token's logit */
+    float* top2;           /* the runner-up's */
+    int32_t n_tokens;
+    int32_t hit_eos;       /* 1: ended by </s>, 0: by the token limit */
+} spt_ms_result;
+
+typedef struct {
+    int32_t d, n_heads, head_dim, rotary_dim, ff, n_enc_layers, n_dec_layers, n_vocab, bos, eos;
+    int32_t dtype, max_batch, max_samples, ctx;
+    int64_t weight_bytes, workspace_bytes;
+} spt_ms_model_info;
+
+typedef struct {
+    double stem_ms, encoder_ms, cross_kv_ms, decode_ms, total_ms;  /* the last device pass */
+    int32_t n_steps;       /* replays of the decode-step graph */
+    int32_t batch;
+} spt_ms_timings;
+
+void spt_moonshine_default_model_params(spt_ms_model_params* p);
+void spt_moonshine_default_infer_params(spt_ms_infer_params* p);
+/* model_spec: "synthetic:moonshine-base|moonshine-tiny|moonshine-test-small[:layers=N][:vocab=V][:eos=E][:seed=S]"
+ * (seeded weights) or "empty:" + the same grammar (every tensor to be supplied by set_tensor).
+ * test-small: Base widths, 2 + 2 layers, vocabulary 1024. */
+spt_status spt_moonshine_create(const char* model_spec, const spt_ms_model_params* params, spt_ms_ctx** out,
+                                char* err, size_t errlen);
+void spt_moonshine_destroy(spt_ms_ctx* ctx);
+const char* spt_moonshine_last_error(const spt_ms_ctx* ctx);
+spt_status spt_moonshine_info(const spt_ms_ctx* ctx, spt_ms_model_info* info);
+/* tensors by HF state-dict name ("model.encoder.conv1.weight", "model.decoder.layers.3.mlp.fc1.bias"):
+ * f32 host data in HF's layout.  The tied "proj_out.weight" is accepted after embed_tokens when it
+ * rounds to the same f16 values, and is never required. */
+spt_status spt_moonshine_tensor_numel(const spt_ms_ctx* ctx, const char* name, int64_t* n);
+spt_status spt_moonshine_set_tensor(spt_ms_ctx* ctx, const char* name, const float* data, int64_t n);
+/* tensors still to be supplied (transcribing with any missing is an error); -1 for a null context */
+int32_t spt_moonshine_missing_tensors(const spt_ms_ctx* ctx);
+/* SentencePiece pieces by id (UTF-8); copied */
+spt_status spt_moonshine_set_vocab(spt_ms_ctx* ctx, const char* const* pieces, int32_t n);
+/* fewer than 895 samples (no encoder frame): SPT_OK, empty text, no device work */
+spt_status spt_moonshine_transcribe(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples,
+                                    const spt_ms_infer_params* params, spt_ms_result** out);
+/* out: `batch` result pointers, each released by spt_moonshine_result_free */
+spt_status spt_moonshine_transcribe_batch(spt_ms_ctx* ctx, const float* const* pcm, const size_t* n_samples,
+                                          size_t batch, const spt_ms_infer_params* params, spt_ms_result** out);
+void spt_moonshine_result_free(spt_ms_result* r);
+spt_status spt_moonshine_get_timings(const spt_ms_ctx* ctx, spt_ms_timings* t);
+/* test hooks (one utterance of 895..max_samples samples): the stem's output [T3][d] f32 (before the
+ * first encoder layer); the encoder's output [T3][d] f32; the logits [n_prefix][n_vocab] f32 of a
+ * forced token prefix (step s is fed prefix[s]; prefix[0] is normally <s>), one row per replay of
+ * the step graph the free-running loop uses.  T3 = ((((n - 127) / 64 + 1) - 7) / 3 + 1 - 3) / 2 + 1. */
+spt_status spt_moonshine_debug_stem(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples, float* out);
+spt_status spt_moonshine_debug_encode(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples, float* out);
+spt_status spt_moonshine_debug_logits(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples, const int32_t* prefix,
+                                      int32_t n_prefix, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -407,6 +407,121 @@ extern "C" {
     pub fn spt_vad_reset(v: *mut spt_vad, reset_model_state: i32) -> spt_status;
     pub fn spt_vad_last_error(v: *const spt_vad) -> *const c_char;
     pub fn spt_vad_destroy(v: *mut spt_vad);
+
+    // ---- Moonshine (SPT_HAS_MOONSHINE, additive over ABI 14)
+    pub fn spt_moonshine_default_model_params(p: *mut spt_ms_model_params);
+    pub fn spt_moonshine_default_infer_params(p: *mut spt_ms_infer_params);
+    pub fn spt_moonshine_create(
+        model_spec: *const c_char,
+        params: *const spt_ms_model_params,
+        out: *mut *mut spt_ms_ctx,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_moonshine_destroy(ctx: *mut spt_ms_ctx);
+    pub fn spt_moonshine_last_error(ctx: *const spt_ms_ctx) -> *const c_char;
+    pub fn spt_moonshine_info(ctx: *const spt_ms_ctx, info: *mut spt_ms_model_info) -> spt_status;
+    pub fn spt_moonshine_tensor_numel(ctx: *const spt_ms_ctx, name: *const c_char, n: *mut i64) -> spt_status;
+    pub fn spt_moonshine_set_tensor(ctx: *mut spt_ms_ctx, name: *const c_char, data: *const f32, n: i64) -> spt_status;
+    pub fn spt_moonshine_missing_tensors(ctx: *const spt_ms_ctx) -> i32;
+    pub fn spt_moonshine_set_vocab(ctx: *mut spt_ms_ctx, pieces: *const *const c_char, n: i32) -> spt_status;
+    pub fn spt_moonshine_transcribe(
+        ctx: *mut spt_ms_ctx,
+        pcm16k: *const f32,
+        n_samples: usize,
+        params: *const spt_ms_infer_params,
+        out: *mut *mut spt_ms_result,
+    ) -> spt_status;
+    pub fn spt_moonshine_transcribe_batch(
+        ctx: *mut spt_ms_ctx,
+        pcm: *const *const f32,
+        n_samples: *const usize,
+        batch: usize,
+        params: *const spt_ms_infer_params,
+        out: *mut *mut spt_ms_result,
+    ) -> spt_status;
+    pub fn spt_moonshine_result_free(r: *mut spt_ms_result);
+    pub fn spt_moonshine_get_timings(ctx: *const spt_ms_ctx, t: *mut spt_ms_timings) -> spt_status;
+    pub fn spt_moonshine_debug_stem(ctx: *mut spt_ms_ctx, pcm16k: *const f32, n_samples: usize, out: *mut f32) -> spt_status;
+    pub fn spt_moonshine_debug_encode(ctx: *mut spt_ms_ctx, pcm16k: *const f32, n_samples: usize, out: *mut f32) -> spt_status;
+    pub fn spt_moonshine_debug_logits(
+        ctx: *mut spt_ms_ctx,
+        pcm16k: *const f32,
+        n_samples: usize,
+        prefix: *const i32,
+        n_prefix: i32,
+        out: *mut f32,
+    ) -> spt_status;
+}
+
+// ---- Moonshine types
+/// The header's feature macro: the spt_moonshine_* entry points exist.
+pub const SPT_HAS_MOONSHINE: c_int = 1;
+
+/// Opaque Moonshine context.
+#[repr(C)]
+pub struct spt_ms_ctx {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_ms_model_params {
+    pub dtype: i32,
+    pub device: i32,
+    pub max_batch: i32,
+    pub max_samples: i32,
+    pub seed: u64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_ms_infer_params {
+    pub tokens_per_second: f32,
+    pub max_tokens: i32,
+}
+
+#[repr(C)]
+pub struct spt_ms_result {
+    pub text: *mut c_char,
+    pub tokens: *mut i32,
+    pub top1: *mut f32,
+    pub top2: *mut f32,
+    pub n_tokens: i32,
+    pub hit_eos: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct spt_ms_model_info {
+    pub d: i32,
+    pub n_heads: i32,
+    pub head_dim: i32,
+    pub rotary_dim: i32,
+    pub ff: i32,
+    pub n_enc_layers: i32,
+    pub n_dec_layers: i32,
+    pub n_vocab: i32,
+    pub bos: i32,
+    pub eos: i32,
+    pub dtype: i32,
+    pub max_batch: i32,
+    pub max_samples: i32,
+    pub ctx: i32,
+    pub weight_bytes: i64,
+    pub workspace_bytes: i64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct spt_ms_timings {
+    pub stem_ms: f64,
+    pub encoder_ms: f64,
+    pub cross_kv_ms: f64,
+    pub decode_ms: f64,
+    pub total_ms: f64,
+    pub n_steps: i32,
+    pub batch: i32,
 }
 
 /// Opaque parsed Parakeet model directory (ABI 8).

@@ -501,6 +501,155 @@ impl Drop for HipParakeetEngine {
     }
 }
 
+/// Which Moonshine geometry a model path holds (transcribe-rs' `ModelVariant`).
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum HipMoonshineVariant {
+    Tiny,
+    Base,
+}
+
+/// Counterpart of `MoonshineModelParams::variant(ModelVariant::Base)`.
+#[derive(Clone, Copy, Debug)]
+pub struct HipMoonshineModelParams {
+    pub variant: HipMoonshineVariant,
+    pub device: i32,
+    pub max_batch: i32,
+    /// the longest utterance taken, in 16 kHz samples (default 64 s)
+    pub max_samples: i32,
+}
+
+impl HipMoonshineModelParams {
+    pub fn variant(variant: HipMoonshineVariant) -> Self {
+        Self { variant, device: 0, max_batch: 1, max_samples: 64 * 16000 }
+    }
+}
+
+impl Default for HipMoonshineModelParams {
+    fn default() -> Self {
+        Self::variant(HipMoonshineVariant::Base)
+    }
+}
+
+/// `LoadedEngine::Moonshine` over the device (spt_moonshine_*).  `model_path` is a model spec the
+/// library takes ("synthetic:moonshine-base", "empty:moonshine-base" + `set_tensor` per HF
+/// state-dict name); the app's ONNX download is not read yet.
+pub struct HipMoonshineEngine {
+    ctx: *mut sys::spt_ms_ctx,
+}
+
+// SAFETY: as for HipWhisperEngine (calls serialised by the app's Mutex; not thread-affine)
+unsafe impl Send for HipMoonshineEngine {}
+
+impl HipMoonshineEngine {
+    pub fn new() -> Self {
+        Self { ctx: std::ptr::null_mut() }
+    }
+
+    fn last_error(&self) -> String {
+        // SAFETY: accepts any context pointer (a static string for null)
+        unsafe { CStr::from_ptr(sys::spt_moonshine_last_error(self.ctx)).to_string_lossy().into_owned() }
+    }
+
+    /// One weight tensor (f32, HF layout) by HF state-dict name.
+    pub fn set_tensor(&mut self, name: &str, data: &[f32]) -> Result<(), Box<dyn Error>> {
+        let cname = CString::new(name)?;
+        // SAFETY: name and data are valid for the duration of the call
+        let st = unsafe { sys::spt_moonshine_set_tensor(self.ctx, cname.as_ptr(), data.as_ptr(), data.len() as i64) };
+        if st != sys::SPT_OK {
+            return Err(status_error("set_tensor", st, self.last_error()));
+        }
+        Ok(())
+    }
+
+    /// SentencePiece pieces by id (tokenizer.json's model.vocab and added_tokens).
+    pub fn set_vocab(&mut self, pieces: &[String]) -> Result<(), Box<dyn Error>> {
+        let owned = pieces.iter().map(|p| CString::new(p.as_bytes())).collect::<Result<Vec<_>, _>>()?;
+        let ptrs: Vec<*const c_char> = owned.iter().map(|p| p.as_ptr()).collect();
+        // SAFETY: the pointers live until the call returns; the library copies the strings
+        let st = unsafe { sys::spt_moonshine_set_vocab(self.ctx, ptrs.as_ptr(), ptrs.len() as i32) };
+        if st != sys::SPT_OK {
+            return Err(status_error("set_vocab", st, self.last_error()));
+        }
+        Ok(())
+    }
+
+    pub fn load_model_with_params(&mut self, model_path: &Path, params: HipMoonshineModelParams) -> Result<(), Box<dyn Error>> {
+        self.unload_model();
+        let spec = CString::new(model_path.to_string_lossy().as_bytes())?;
+        let mut mp = std::mem::MaybeUninit::<sys::spt_ms_model_params>::uninit();
+        // SAFETY: fills every field
+        let mut mp = unsafe {
+            sys::spt_moonshine_default_model_params(mp.as_mut_ptr());
+            mp.assume_init()
+        };
+        mp.device = params.device;
+        mp.max_batch = params.max_batch;
+        mp.max_samples = params.max_samples;
+        let mut err = vec![0 as c_char; 1024];
+        let mut ctx = std::ptr::null_mut();
+        // SAFETY: valid C strings and out-pointers for the duration of the call
+        let st = unsafe { sys::spt_moonshine_create(spec.as_ptr(), &mp, &mut ctx, err.as_mut_ptr(), err.len()) };
+        if st != sys::SPT_OK {
+            // SAFETY: the library NUL-terminates err
+            let msg = unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned();
+            return Err(status_error("model load", st, msg));
+        }
+        self.ctx = ctx;
+        let mut info = sys::spt_ms_model_info::default();
+        // SAFETY: a live context and a valid out-pointer
+        unsafe { sys::spt_moonshine_info(self.ctx, &mut info) };
+        let want = match params.variant {
+            HipMoonshineVariant::Base => 416,
+            HipMoonshineVariant::Tiny => 288,
+        };
+        if info.d != want {
+            self.unload_model();
+            return Err(format!("model width {} does not match the requested variant ({})", info.d, want).into());
+        }
+        Ok(())
+    }
+
+    pub fn unload_model(&mut self) {
+        if !self.ctx.is_null() {
+            // SAFETY: created by spt_moonshine_create, destroyed once
+            unsafe { sys::spt_moonshine_destroy(self.ctx) };
+            self.ctx = std::ptr::null_mut();
+        }
+    }
+
+    /// `transcribe_samples(audio, None)`: greedy decoding to </s> or ceil(6.5 tokens per second).
+    pub fn transcribe_samples(&mut self, samples: Vec<f32>) -> Result<TranscriptionResult, Box<dyn Error>> {
+        if self.ctx.is_null() {
+            return Err("Model is not loaded for transcription.".into());
+        }
+        let mut out = std::ptr::null_mut();
+        // SAFETY: samples outlives the call; null params = the defaults; out receives a library-owned result
+        let st = unsafe { sys::spt_moonshine_transcribe(self.ctx, samples.as_ptr(), samples.len(), std::ptr::null(), &mut out) };
+        if st != sys::SPT_OK {
+            return Err(status_error("transcription", st, self.last_error()));
+        }
+        // SAFETY: a successful call returns a live result, read then freed once
+        unsafe {
+            let res = &*out;
+            let text = if res.text.is_null() { String::new() } else { CStr::from_ptr(res.text).to_string_lossy().into_owned() };
+            sys::spt_moonshine_result_free(out);
+            Ok(TranscriptionResult { text, segments: None })
+        }
+    }
+}
+
+impl Default for HipMoonshineEngine {
+    fn default() -> Self {
+        Self::new()
+    }
+}
+
+impl Drop for HipMoonshineEngine {
+    fn drop(&mut self) {
+        self.unload_model();
+    }
+}
+
 /// The capture-side resampler (ABI 7): `FrameResampler` of
 /// /root/reference/src-tauri/src/audio_toolkit/audio/resampler.rs:7-104 over the device.
 /// `process_stream` = `FrameResampler::new(in_hz, out_hz, frame_dur)` + `push(all)` + `finish`

@@ -1,4 +1,4 @@
-"""spittle_amd -- MI355X-native (gfx950) Whisper and Parakeet-V3 transcription backend for Spittle.
+"""spittle_amd -- MI355X-native (gfx950) Whisper, Parakeet-V3 and Moonshine transcription backend for Spittle.
 
 The hot path (log-mel, encoder, cross-attention K/V, greedy decoder loop) is
 hand-written HIP in spittle_amd/csrc, exported through the C ABI in
@@ -11,6 +11,10 @@ from .engine import (TranscriptionError, TranscriptionResult, TranscriptionSegme
 from .parakeet import (ParakeetEngine, ParakeetInferenceParams, ParakeetModelParams, ParakeetResult,
                        TimestampGranularity)
 
-__all__ = ["ParakeetEngine", "ParakeetInferenceParams", "ParakeetModelParams", "ParakeetResult",
+from .moonshine import (ModelVariant, MoonshineEngine, MoonshineInferenceParams, MoonshineModelParams,
+                        MoonshineResult)
+
+__all__ = ["ModelVariant", "MoonshineEngine", "MoonshineInferenceParams", "MoonshineModelParams", "MoonshineResult",
+           "ParakeetEngine", "ParakeetInferenceParams", "ParakeetModelParams", "ParakeetResult",
            "TimestampGranularity", "WhisperEngine", "WhisperInferenceParams", "WhisperModelParams", "TranscriptionResult",
            "TranscriptionSegment", "TranscriptionError"]

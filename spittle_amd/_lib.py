@@ -44,6 +44,12 @@ EXPORTS = [
     "spt_parakeet_profile_encoder",
     # ABI 13: the Parakeet encoder's int8 mode (SPT_DTYPE_I8)
     "spt_parakeet_onnx_qtensor", "spt_parakeet_debug_qgemm", "spt_parakeet_debug_tap", "spt_parakeet_debug_tap_read",
+    # Moonshine (SPT_HAS_MOONSHINE, additive over ABI 14)
+    "spt_moonshine_default_model_params", "spt_moonshine_default_infer_params", "spt_moonshine_create",
+    "spt_moonshine_destroy", "spt_moonshine_last_error", "spt_moonshine_info", "spt_moonshine_tensor_numel",
+    "spt_moonshine_set_tensor", "spt_moonshine_missing_tensors", "spt_moonshine_set_vocab", "spt_moonshine_transcribe",
+    "spt_moonshine_transcribe_batch", "spt_moonshine_result_free", "spt_moonshine_get_timings",
+    "spt_moonshine_debug_stem", "spt_moonshine_debug_encode", "spt_moonshine_debug_logits",
 ]
 SPT_PK_WEIGHTS_EMPTY = 1
 SPT_PK_TS_TOKEN, SPT_PK_TS_WORD, SPT_PK_TS_SEGMENT = 0, 1, 2
@@ -128,6 +134,32 @@ class PkModelInfo(C.Structure):
 class PkTimings(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("mel_ms", "encoder_ms", "decode_ms", "total_ms", "h2d_ms")] + \
                [(n, C.c_int32) for n in ("n_steps", "batch", "enc_frames", "reserved0")]
+
+
+class MsModelParams(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("device", C.c_int32), ("max_batch", C.c_int32), ("max_samples", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class MsInferParams(C.Structure):
+    _fields_ = [("tokens_per_second", C.c_float), ("max_tokens", C.c_int32)]
+
+
+class MsResult(C.Structure):
+    _fields_ = [("text", C.c_char_p), ("tokens", C.POINTER(C.c_int32)), ("top1", C.POINTER(C.c_float)),
+                ("top2", C.POINTER(C.c_float)), ("n_tokens", C.c_int32), ("hit_eos", C.c_int32)]
+
+
+class MsModelInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d", "n_heads", "head_dim", "rotary_dim", "ff", "n_enc_layers",
+                                          "n_dec_layers", "n_vocab", "bos", "eos", "dtype", "max_batch",
+                                          "max_samples", "ctx")] + \
+               [("weight_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
+
+
+class MsTimings(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("stem_ms", "encoder_ms", "cross_kv_ms", "decode_ms", "total_ms")] + \
+               [("n_steps", C.c_int32), ("batch", C.c_int32)]
 
 
 class VadParams(C.Structure):
@@ -262,6 +294,37 @@ def load():
     L.spt_vad_last_error.restype = C.c_char_p
     L.spt_vad_destroy.argtypes = [vp]
     L.spt_vad_destroy.restype = None
+    # Moonshine
+    MR = C.POINTER(C.POINTER(MsResult))
+    L.spt_moonshine_default_model_params.argtypes = [C.POINTER(MsModelParams)]
+    L.spt_moonshine_default_model_params.restype = None
+    L.spt_moonshine_default_infer_params.argtypes = [C.POINTER(MsInferParams)]
+    L.spt_moonshine_default_infer_params.restype = None
+    L.spt_moonshine_create.argtypes = [C.c_char_p, C.POINTER(MsModelParams), C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.spt_moonshine_destroy.argtypes = [vp]
+    L.spt_moonshine_destroy.restype = None
+    L.spt_moonshine_last_error.argtypes = [vp]
+    L.spt_moonshine_last_error.restype = C.c_char_p
+    L.spt_moonshine_info.argtypes = [vp, C.POINTER(MsModelInfo)]
+    L.spt_moonshine_tensor_numel.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+    L.spt_moonshine_set_tensor.argtypes = [vp, C.c_char_p, fp, C.c_int64]
+    L.spt_moonshine_missing_tensors.argtypes = [vp]
+    L.spt_moonshine_missing_tensors.restype = C.c_int32
+    L.spt_moonshine_set_vocab.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int32]
+    L.spt_moonshine_transcribe.argtypes = [vp, fp, C.c_size_t, C.POINTER(MsInferParams), MR]
+    L.spt_moonshine_transcribe_batch.argtypes = [vp, C.POINTER(fp), C.POINTER(C.c_size_t), C.c_size_t,
+                                                 C.POINTER(MsInferParams), MR]
+    L.spt_moonshine_result_free.argtypes = [C.POINTER(MsResult)]
+    L.spt_moonshine_result_free.restype = None
+    L.spt_moonshine_get_timings.argtypes = [vp, C.POINTER(MsTimings)]
+    L.spt_moonshine_debug_stem.argtypes = [vp, fp, C.c_size_t, fp]
+    L.spt_moonshine_debug_encode.argtypes = [vp, fp, C.c_size_t, fp]
+    L.spt_moonshine_debug_logits.argtypes = [vp, fp, C.c_size_t, i32p, C.c_int32, fp]
+    for fn in ("spt_moonshine_create", "spt_moonshine_info", "spt_moonshine_tensor_numel", "spt_moonshine_set_tensor",
+               "spt_moonshine_set_vocab", "spt_moonshine_transcribe", "spt_moonshine_transcribe_batch",
+               "spt_moonshine_get_timings", "spt_moonshine_debug_stem", "spt_moonshine_debug_encode",
+               "spt_moonshine_debug_logits"):
+        getattr(L, fn).restype = C.c_int
     for fn in EXPORTS:
         if fn.startswith("spt_parakeet_") and fn not in ("spt_parakeet_default_model_params",
                                                           "spt_parakeet_default_infer_params", "spt_parakeet_destroy",
