@@ -632,6 +632,121 @@ spt_status spt_moonshine_debug_encode(spt_ms_ctx* ctx, const float* pcm16k, size
 spt_status spt_moonshine_debug_logits(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples, const int32_t* prefix,
                                       int32_t n_prefix, float* out);
 
+/* ================================================================================================
+ * SenseVoice (additive over ABI 14, announced by SPT_HAS_SENSEVOICE): the app's fourth local engine.
+ *
+ * Replaces transcribe_rs::engines::sense_voice::SenseVoiceEngine as TranscriptionManager drives it
+ * through `LoadedEngine::SenseVoice` (src-tauri/src/managers/transcription.rs:260-341, 444-534):
+ *
+ *   load_model_with_params(&path, SenseVoiceModelParams::int8())       -> spt_sensevoice_create
+ *   transcribe_samples(audio, Some(SenseVoiceInferenceParams{..}))     -> spt_sensevoice_transcribe
+ *   unload_model() / Drop                                              -> spt_sensevoice_destroy
+ *
+ * SenseVoice-Small is non-autoregressive: a Kaldi fbank (80 mels, 25 ms / 10 ms, Hamming) stacked to
+ * low-frame-rate rows (7 frames every 6), four query rows (language, event, emotion, text norm) in
+ * front, a 70-layer SANM encoder (self-attention with head dim 128 plus an 11-tap FSMN memory) and a
+ * CTC head; one forward pass per call, greedy collapse on the device.  A batch row computes what it
+ * computes alone.  Engine dtype is fp16 only: f16 weights and GEMM inputs, f32 accumulation, residual
+ * stream, norms, softmax and front end.  Weights come from a synthetic spec or tensor by tensor, keyed
+ * by FunASR state-dict name.  The encoder's constants recalled from FunASR without a copy to check
+ * against are model parameters with the recalled defaults.  DESIGN.md §13 is the contract.
+ * ============================================================================================== */
+#define SPT_HAS_SENSEVOICE 1
+
+typedef struct spt_sv_ctx spt_sv_ctx;
+
+enum { SPT_SV_LANG_AUTO = 0, SPT_SV_LANG_ZH = 1, SPT_SV_LANG_EN = 2, SPT_SV_LANG_YUE = 3, SPT_SV_LANG_JA = 4,
+       SPT_SV_LANG_KO = 5 };
+
+typedef struct {
+    int32_t dtype;        /* SPT_DTYPE_F16 (default); every other dtype: SPT_ERR_UNSUPPORTED */
+    int32_t device;
+    int32_t max_batch;    /* utterances per device pass, <= 64 (default 8); longer batches run in passes */
+    int32_t max_samples;  /* the longest utterance taken: 400..4800000 (300 s), default 64 s = 1024000;
+                             a longer utterance: SPT_ERR_INVALID_ARG */
+    uint64_t seed;        /* synthetic weights (a ":seed=S" in the spec wins) */
+    /* recalled from FunASR's SenseVoiceSmall, unverifiable offline: defaults as recalled */
+    float ln_eps;         /* LayerNorm epsilon, default 1e-5 */
+    int32_t sanm_shift;   /* FSMN padding: 5 + shift frames left, 5 - shift right; default 0 */
+    int32_t lfr_m;        /* frames stacked per row, default 7 (the embed / CMVN width is 80 * lfr_m) */
+    int32_t lfr_n;        /* frames advanced per row, default 6 */
+    int32_t blank_id;     /* CTC blank, default 0 */
+    int32_t n_prefix;     /* leading output rows reported as labels, not text: 0..4, default 4 */
+    int32_t lang_rows[6]; /* embed row of each SPT_SV_LANG_*: default 0, 3, 4, 7, 11, 12 */
+    int32_t event_row;    /* default 1 */
+    int32_t emo_row;      /* default 2 */
+    int32_t itn_row;      /* text norm row with ITN, default 14 */
+    int32_t no_itn_row;   /* without, default 15 */
+} spt_sv_model_params;
+
+typedef struct {
+    int32_t language;     /* SPT_SV_LANG_*; default AUTO */
+    int32_t use_itn;      /* default 0 */
+} spt_sv_infer_params;
+
+typedef struct {
+    char* text;            /* pieces joined: "<|..|>" tags and specials dropped, byte pieces to bytes, "▁" ->
+                              space, leading space stripped; "[id]" per token without a vocabulary */
+    int32_t* tokens;       /* collapsed ids, blanks dropped */
+    int32_t* frames;       /* the row (after the prefix rows) where each token's run starts: 60 ms units */
+    float* top1;           /* that row's top logit */
+    float* top2;           /* and its runner-up */
+    int32_t n_tokens;
+    int32_t prefix[4];     /* argmax of output rows 0..3: language, emotion, event, ITN tags (-1 beyond n_prefix) */
+} spt_sv_result;
+
+typedef struct {
+    int32_t d, n_heads, head_dim, ff, n_enc0_layers, n_enc_layers, n_tp_layers, n_vocab, input_dim;
+    int32_t dtype, max_batch, max_samples, max_rows, reserved;
+    int64_t weight_bytes, workspace_bytes;
+} spt_sv_model_info;
+
+typedef struct {
+    double frontend_ms, encoder_ms, ctc_ms, total_ms;  /* the last device pass */
+    int32_t rows;          /* encoder rows per utterance of that pass (the longest) */
+    int32_t batch;
+} spt_sv_timings;
+
+void spt_sensevoice_default_model_params(spt_sv_model_params* p);
+void spt_sensevoice_default_infer_params(spt_sv_infer_params* p);
+/* model_spec: "synthetic:sensevoice-small|sensevoice-test-small[:layers=a,b][:vocab=V][:seed=S]" (seeded
+ * weights and a fixed CMVN) or "empty:" + the same grammar (every tensor by set_tensor, the CMVN by
+ * set_cmvn).  layers=a,b: encoders / tp_encoders.  test-small: d 256, 2 heads, ff 512, 1 + 2 + 1
+ * layers, vocabulary 500. */
+spt_status spt_sensevoice_create(const char* model_spec, const spt_sv_model_params* params, spt_sv_ctx** out,
+                                 char* err, size_t errlen);
+void spt_sensevoice_destroy(spt_sv_ctx* ctx);
+const char* spt_sensevoice_last_error(const spt_sv_ctx* ctx);
+spt_status spt_sensevoice_info(const spt_sv_ctx* ctx, spt_sv_model_info* info);
+/* tensors by FunASR state-dict name ("embed.weight", "encoder.encoders.3.self_attn.fsmn_block.weight",
+ * "ctc.ctc_lo.bias"): f32 host data in FunASR's layout */
+spt_status spt_sensevoice_tensor_numel(const spt_sv_ctx* ctx, const char* name, int64_t* n);
+spt_status spt_sensevoice_set_tensor(spt_sv_ctx* ctx, const char* name, const float* data, int64_t n);
+/* tensors still to be supplied, the CMVN pair counting as one; -1 for a null context */
+int32_t spt_sensevoice_missing_tensors(const spt_sv_ctx* ctx);
+/* features = (lfr + neg_mean) * inv_std, n = 80 * lfr_m values each (am.mvn's <AddShift> / <Rescale>) */
+spt_status spt_sensevoice_set_cmvn(spt_sv_ctx* ctx, const float* neg_mean, const float* inv_std, int32_t n);
+/* SentencePiece pieces by id (UTF-8); copied */
+spt_status spt_sensevoice_set_vocab(spt_sv_ctx* ctx, const char* const* pieces, int32_t n);
+/* encoder rows of n samples: ceil((1 + (n - 400) / 160) / lfr_n) + 4, or 0 below 400 samples */
+int32_t spt_sensevoice_n_rows(const spt_sv_ctx* ctx, size_t n_samples);
+/* fewer than 400 samples (no fbank frame): SPT_OK, empty text, no device work */
+spt_status spt_sensevoice_transcribe(spt_sv_ctx* ctx, const float* pcm16k, size_t n_samples,
+                                     const spt_sv_infer_params* params, spt_sv_result** out);
+/* out: `batch` result pointers, each released by spt_sensevoice_result_free */
+spt_status spt_sensevoice_transcribe_batch(spt_sv_ctx* ctx, const float* const* pcm, const size_t* n_samples,
+                                           size_t batch, const spt_sv_infer_params* params, spt_sv_result** out);
+void spt_sensevoice_result_free(spt_sv_result* r);
+spt_status spt_sensevoice_get_timings(const spt_sv_ctx* ctx, spt_sv_timings* t);
+/* test hooks (one utterance of 400..max_samples samples, R = spt_sensevoice_n_rows): the LFR rows after
+ * CMVN, before the queries [R - 4][input_dim] f32; the encoder output after tp_norm [R][d] f32; per row
+ * the top-1 id and the top-1 / top-2 logits over the real vocabulary [R] each */
+spt_status spt_sensevoice_debug_features(spt_sv_ctx* ctx, const float* pcm16k, size_t n_samples, float* out);
+spt_status spt_sensevoice_debug_encode(spt_sv_ctx* ctx, const float* pcm16k, size_t n_samples,
+                                       const spt_sv_infer_params* params, float* out);
+spt_status spt_sensevoice_debug_frames(spt_sv_ctx* ctx, const float* pcm16k, size_t n_samples,
+                                       const spt_sv_infer_params* params, int32_t* ids, float* top1, float* top2);
+
 #ifdef __cplusplus
 }
 #endif

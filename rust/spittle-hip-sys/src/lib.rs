@@ -452,6 +452,147 @@ extern "C" {
         n_prefix: i32,
         out: *mut f32,
     ) -> spt_status;
+
+    // ---- SenseVoice (SPT_HAS_SENSEVOICE, additive over ABI 14)
+    pub fn spt_sensevoice_default_model_params(p: *mut spt_sv_model_params);
+    pub fn spt_sensevoice_default_infer_params(p: *mut spt_sv_infer_params);
+    pub fn spt_sensevoice_create(
+        model_spec: *const c_char,
+        params: *const spt_sv_model_params,
+        out: *mut *mut spt_sv_ctx,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_sensevoice_destroy(ctx: *mut spt_sv_ctx);
+    pub fn spt_sensevoice_last_error(ctx: *const spt_sv_ctx) -> *const c_char;
+    pub fn spt_sensevoice_info(ctx: *const spt_sv_ctx, info: *mut spt_sv_model_info) -> spt_status;
+    pub fn spt_sensevoice_tensor_numel(ctx: *const spt_sv_ctx, name: *const c_char, n: *mut i64) -> spt_status;
+    pub fn spt_sensevoice_set_tensor(ctx: *mut spt_sv_ctx, name: *const c_char, data: *const f32, n: i64) -> spt_status;
+    pub fn spt_sensevoice_missing_tensors(ctx: *const spt_sv_ctx) -> i32;
+    pub fn spt_sensevoice_set_cmvn(ctx: *mut spt_sv_ctx, neg_mean: *const f32, inv_std: *const f32, n: i32) -> spt_status;
+    pub fn spt_sensevoice_set_vocab(ctx: *mut spt_sv_ctx, pieces: *const *const c_char, n: i32) -> spt_status;
+    pub fn spt_sensevoice_n_rows(ctx: *const spt_sv_ctx, n_samples: usize) -> i32;
+    pub fn spt_sensevoice_transcribe(
+        ctx: *mut spt_sv_ctx,
+        pcm16k: *const f32,
+        n_samples: usize,
+        params: *const spt_sv_infer_params,
+        out: *mut *mut spt_sv_result,
+    ) -> spt_status;
+    pub fn spt_sensevoice_transcribe_batch(
+        ctx: *mut spt_sv_ctx,
+        pcm: *const *const f32,
+        n_samples: *const usize,
+        batch: usize,
+        params: *const spt_sv_infer_params,
+        out: *mut *mut spt_sv_result,
+    ) -> spt_status;
+    pub fn spt_sensevoice_result_free(r: *mut spt_sv_result);
+    pub fn spt_sensevoice_get_timings(ctx: *const spt_sv_ctx, t: *mut spt_sv_timings) -> spt_status;
+    pub fn spt_sensevoice_debug_features(ctx: *mut spt_sv_ctx, pcm16k: *const f32, n_samples: usize, out: *mut f32) -> spt_status;
+    pub fn spt_sensevoice_debug_encode(
+        ctx: *mut spt_sv_ctx,
+        pcm16k: *const f32,
+        n_samples: usize,
+        params: *const spt_sv_infer_params,
+        out: *mut f32,
+    ) -> spt_status;
+    pub fn spt_sensevoice_debug_frames(
+        ctx: *mut spt_sv_ctx,
+        pcm16k: *const f32,
+        n_samples: usize,
+        params: *const spt_sv_infer_params,
+        ids: *mut i32,
+        top1: *mut f32,
+        top2: *mut f32,
+    ) -> spt_status;
+}
+
+// ---- SenseVoice types
+/// The header's feature macro: the spt_sensevoice_* entry points exist.
+pub const SPT_HAS_SENSEVOICE: c_int = 1;
+pub const SPT_SV_LANG_AUTO: i32 = 0;
+pub const SPT_SV_LANG_ZH: i32 = 1;
+pub const SPT_SV_LANG_EN: i32 = 2;
+pub const SPT_SV_LANG_YUE: i32 = 3;
+pub const SPT_SV_LANG_JA: i32 = 4;
+pub const SPT_SV_LANG_KO: i32 = 5;
+
+/// Opaque SenseVoice context.
+#[repr(C)]
+pub struct spt_sv_ctx {
+    _private: [u8; 0],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_sv_model_params {
+    pub dtype: i32,
+    pub device: i32,
+    pub max_batch: i32,
+    pub max_samples: i32,
+    pub seed: u64,
+    pub ln_eps: f32,
+    pub sanm_shift: i32,
+    pub lfr_m: i32,
+    pub lfr_n: i32,
+    pub blank_id: i32,
+    pub n_prefix: i32,
+    pub lang_rows: [i32; 6],
+    pub event_row: i32,
+    pub emo_row: i32,
+    pub itn_row: i32,
+    pub no_itn_row: i32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_sv_infer_params {
+    pub language: i32,
+    pub use_itn: i32,
+}
+
+#[repr(C)]
+pub struct spt_sv_result {
+    pub text: *mut c_char,
+    pub tokens: *mut i32,
+    pub frames: *mut i32,
+    pub top1: *mut f32,
+    pub top2: *mut f32,
+    pub n_tokens: i32,
+    pub prefix: [i32; 4],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct spt_sv_model_info {
+    pub d: i32,
+    pub n_heads: i32,
+    pub head_dim: i32,
+    pub ff: i32,
+    pub n_enc0_layers: i32,
+    pub n_enc_layers: i32,
+    pub n_tp_layers: i32,
+    pub n_vocab: i32,
+    pub input_dim: i32,
+    pub dtype: i32,
+    pub max_batch: i32,
+    pub max_samples: i32,
+    pub max_rows: i32,
+    pub reserved: i32,
+    pub weight_bytes: i64,
+    pub workspace_bytes: i64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct spt_sv_timings {
+    pub frontend_ms: f64,
+    pub encoder_ms: f64,
+    pub ctc_ms: f64,
+    pub total_ms: f64,
+    pub rows: i32,
+    pub batch: i32,
 }
 
 // ---- Moonshine types

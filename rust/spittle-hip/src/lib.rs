@@ -650,6 +650,199 @@ impl Drop for HipMoonshineEngine {
     }
 }
 
+/// transcribe-rs' `sense_voice::Language`.
+#[derive(Clone, Copy, Debug, PartialEq, Eq, Default)]
+pub enum HipSenseVoiceLanguage {
+    #[default]
+    Auto,
+    Chinese,
+    English,
+    Cantonese,
+    Japanese,
+    Korean,
+}
+
+impl HipSenseVoiceLanguage {
+    /// The app's `selected_language` mapping (transcription.rs:518-525).
+    pub fn from_code(code: &str) -> Self {
+        match code {
+            "zh" | "zh-Hans" | "zh-Hant" => Self::Chinese,
+            "en" => Self::English,
+            "ja" => Self::Japanese,
+            "ko" => Self::Korean,
+            "yue" => Self::Cantonese,
+            _ => Self::Auto,
+        }
+    }
+
+    fn to_sys(self) -> i32 {
+        match self {
+            Self::Auto => sys::SPT_SV_LANG_AUTO,
+            Self::Chinese => sys::SPT_SV_LANG_ZH,
+            Self::English => sys::SPT_SV_LANG_EN,
+            Self::Cantonese => sys::SPT_SV_LANG_YUE,
+            Self::Japanese => sys::SPT_SV_LANG_JA,
+            Self::Korean => sys::SPT_SV_LANG_KO,
+        }
+    }
+}
+
+/// Counterpart of `SenseVoiceModelParams::int8()`; the engine itself runs fp16.
+#[derive(Clone, Copy, Debug)]
+pub struct HipSenseVoiceModelParams {
+    pub device: i32,
+    pub max_batch: i32,
+    /// the longest utterance taken, in 16 kHz samples (default 64 s)
+    pub max_samples: i32,
+}
+
+impl HipSenseVoiceModelParams {
+    pub fn int8() -> Self {
+        Self { device: 0, max_batch: 1, max_samples: 64 * 16000 }
+    }
+}
+
+impl Default for HipSenseVoiceModelParams {
+    fn default() -> Self {
+        Self::int8()
+    }
+}
+
+/// Counterpart of `SenseVoiceInferenceParams { language, use_itn }`.
+#[derive(Clone, Copy, Debug, Default)]
+pub struct HipSenseVoiceInferenceParams {
+    pub language: HipSenseVoiceLanguage,
+    pub use_itn: bool,
+}
+
+/// `LoadedEngine::SenseVoice` over the device (spt_sensevoice_*).  `model_path` is a model spec the
+/// library takes ("synthetic:sensevoice-small", "empty:sensevoice-small" + `set_tensor` per FunASR
+/// state-dict name + `set_cmvn`); the app's int8 ONNX download is not read.
+pub struct HipSenseVoiceEngine {
+    ctx: *mut sys::spt_sv_ctx,
+}
+
+// SAFETY: as for HipWhisperEngine (calls serialised by the app's Mutex; not thread-affine)
+unsafe impl Send for HipSenseVoiceEngine {}
+
+impl HipSenseVoiceEngine {
+    pub fn new() -> Self {
+        Self { ctx: std::ptr::null_mut() }
+    }
+
+    fn last_error(&self) -> String {
+        // SAFETY: accepts any context pointer (a static string for null)
+        unsafe { CStr::from_ptr(sys::spt_sensevoice_last_error(self.ctx)).to_string_lossy().into_owned() }
+    }
+
+    /// One weight tensor (f32, FunASR layout) by FunASR state-dict name.
+    pub fn set_tensor(&mut self, name: &str, data: &[f32]) -> Result<(), Box<dyn Error>> {
+        let cname = CString::new(name)?;
+        // SAFETY: name and data are valid for the duration of the call
+        let st = unsafe { sys::spt_sensevoice_set_tensor(self.ctx, cname.as_ptr(), data.as_ptr(), data.len() as i64) };
+        if st != sys::SPT_OK {
+            return Err(status_error("set_tensor", st, self.last_error()));
+        }
+        Ok(())
+    }
+
+    /// am.mvn's `<AddShift>` and `<Rescale>` vectors: features = (lfr + neg_mean) * inv_std.
+    pub fn set_cmvn(&mut self, neg_mean: &[f32], inv_std: &[f32]) -> Result<(), Box<dyn Error>> {
+        if neg_mean.len() != inv_std.len() {
+            return Err("CMVN vectors differ in length".into());
+        }
+        // SAFETY: both slices are valid for the duration of the call
+        let st = unsafe { sys::spt_sensevoice_set_cmvn(self.ctx, neg_mean.as_ptr(), inv_std.as_ptr(), neg_mean.len() as i32) };
+        if st != sys::SPT_OK {
+            return Err(status_error("set_cmvn", st, self.last_error()));
+        }
+        Ok(())
+    }
+
+    /// SentencePiece pieces by id.
+    pub fn set_vocab(&mut self, pieces: &[String]) -> Result<(), Box<dyn Error>> {
+        let owned = pieces.iter().map(|p| CString::new(p.as_bytes())).collect::<Result<Vec<_>, _>>()?;
+        let ptrs: Vec<*const c_char> = owned.iter().map(|p| p.as_ptr()).collect();
+        // SAFETY: the pointers live until the call returns; the library copies the strings
+        let st = unsafe { sys::spt_sensevoice_set_vocab(self.ctx, ptrs.as_ptr(), ptrs.len() as i32) };
+        if st != sys::SPT_OK {
+            return Err(status_error("set_vocab", st, self.last_error()));
+        }
+        Ok(())
+    }
+
+    pub fn load_model_with_params(&mut self, model_path: &Path, params: HipSenseVoiceModelParams) -> Result<(), Box<dyn Error>> {
+        self.unload_model();
+        let spec = CString::new(model_path.to_string_lossy().as_bytes())?;
+        let mut mp = std::mem::MaybeUninit::<sys::spt_sv_model_params>::uninit();
+        // SAFETY: fills every field
+        let mut mp = unsafe {
+            sys::spt_sensevoice_default_model_params(mp.as_mut_ptr());
+            mp.assume_init()
+        };
+        mp.device = params.device;
+        mp.max_batch = params.max_batch;
+        mp.max_samples = params.max_samples;
+        let mut err = vec![0 as c_char; 1024];
+        let mut ctx = std::ptr::null_mut();
+        // SAFETY: valid C strings and out-pointers for the duration of the call
+        let st = unsafe { sys::spt_sensevoice_create(spec.as_ptr(), &mp, &mut ctx, err.as_mut_ptr(), err.len()) };
+        if st != sys::SPT_OK {
+            // SAFETY: the library NUL-terminates err
+            let msg = unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned();
+            return Err(status_error("model load", st, msg));
+        }
+        self.ctx = ctx;
+        Ok(())
+    }
+
+    pub fn unload_model(&mut self) {
+        if !self.ctx.is_null() {
+            // SAFETY: created by spt_sensevoice_create, destroyed once
+            unsafe { sys::spt_sensevoice_destroy(self.ctx) };
+            self.ctx = std::ptr::null_mut();
+        }
+    }
+
+    /// `transcribe_samples(audio, Some(params))`: one forward pass and the CTC greedy collapse.
+    pub fn transcribe_samples(
+        &mut self,
+        samples: Vec<f32>,
+        params: Option<HipSenseVoiceInferenceParams>,
+    ) -> Result<TranscriptionResult, Box<dyn Error>> {
+        if self.ctx.is_null() {
+            return Err("Model is not loaded for transcription.".into());
+        }
+        let p = params.unwrap_or_default();
+        let ip = sys::spt_sv_infer_params { language: p.language.to_sys(), use_itn: p.use_itn as i32 };
+        let mut out = std::ptr::null_mut();
+        // SAFETY: samples and ip outlive the call; out receives a library-owned result
+        let st = unsafe { sys::spt_sensevoice_transcribe(self.ctx, samples.as_ptr(), samples.len(), &ip, &mut out) };
+        if st != sys::SPT_OK {
+            return Err(status_error("transcription", st, self.last_error()));
+        }
+        // SAFETY: a successful call returns a live result, read then freed once
+        unsafe {
+            let res = &*out;
+            let text = if res.text.is_null() { String::new() } else { CStr::from_ptr(res.text).to_string_lossy().into_owned() };
+            sys::spt_sensevoice_result_free(out);
+            Ok(TranscriptionResult { text, segments: None })
+        }
+    }
+}
+
+impl Default for HipSenseVoiceEngine {
+    fn default() -> Self {
+        Self::new()
+    }
+}
+
+impl Drop for HipSenseVoiceEngine {
+    fn drop(&mut self) {
+        self.unload_model();
+    }
+}
+
 /// The capture-side resampler (ABI 7): `FrameResampler` of
 /// /root/reference/src-tauri/src/audio_toolkit/audio/resampler.rs:7-104 over the device.
 /// `process_stream` = `FrameResampler::new(in_hz, out_hz, frame_dur)` + `push(all)` + `finish`

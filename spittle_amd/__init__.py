@@ -1,4 +1,4 @@
-"""spittle_amd -- MI355X-native (gfx950) Whisper, Parakeet-V3 and Moonshine transcription backend for Spittle.
+"""spittle_amd -- MI355X-native (gfx950) Whisper, Parakeet-V3, Moonshine and SenseVoice transcription backend for Spittle.
 
 The hot path (log-mel, encoder, cross-attention K/V, greedy decoder loop) is
 hand-written HIP in spittle_amd/csrc, exported through the C ABI in
@@ -14,7 +14,11 @@ from .parakeet import (ParakeetEngine, ParakeetInferenceParams, ParakeetModelPar
 from .moonshine import (ModelVariant, MoonshineEngine, MoonshineInferenceParams, MoonshineModelParams,
                         MoonshineResult)
 
-__all__ = ["ModelVariant", "MoonshineEngine", "MoonshineInferenceParams", "MoonshineModelParams", "MoonshineResult",
-           "ParakeetEngine", "ParakeetInferenceParams", "ParakeetModelParams", "ParakeetResult",
+from .sensevoice import (Language, SenseVoiceEngine, SenseVoiceInferenceParams, SenseVoiceModelParams,
+                         SenseVoiceResult)
+
+__all__ = ["Language", "ModelVariant", "MoonshineEngine", "MoonshineInferenceParams", "MoonshineModelParams",
+           "MoonshineResult", "ParakeetEngine", "ParakeetInferenceParams", "ParakeetModelParams", "ParakeetResult",
+           "SenseVoiceEngine", "SenseVoiceInferenceParams", "SenseVoiceModelParams", "SenseVoiceResult",
            "TimestampGranularity", "WhisperEngine", "WhisperInferenceParams", "WhisperModelParams", "TranscriptionResult",
            "TranscriptionSegment", "TranscriptionError"]

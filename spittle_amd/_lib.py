@@ -50,7 +50,15 @@ EXPORTS = [
     "spt_moonshine_set_tensor", "spt_moonshine_missing_tensors", "spt_moonshine_set_vocab", "spt_moonshine_transcribe",
     "spt_moonshine_transcribe_batch", "spt_moonshine_result_free", "spt_moonshine_get_timings",
     "spt_moonshine_debug_stem", "spt_moonshine_debug_encode", "spt_moonshine_debug_logits",
+    # SenseVoice (SPT_HAS_SENSEVOICE, additive over ABI 14)
+    "spt_sensevoice_default_model_params", "spt_sensevoice_default_infer_params", "spt_sensevoice_create",
+    "spt_sensevoice_destroy", "spt_sensevoice_last_error", "spt_sensevoice_info", "spt_sensevoice_tensor_numel",
+    "spt_sensevoice_set_tensor", "spt_sensevoice_missing_tensors", "spt_sensevoice_set_cmvn",
+    "spt_sensevoice_set_vocab", "spt_sensevoice_n_rows", "spt_sensevoice_transcribe",
+    "spt_sensevoice_transcribe_batch", "spt_sensevoice_result_free", "spt_sensevoice_get_timings",
+    "spt_sensevoice_debug_features", "spt_sensevoice_debug_encode", "spt_sensevoice_debug_frames",
 ]
+SPT_SV_LANG_AUTO, SPT_SV_LANG_ZH, SPT_SV_LANG_EN, SPT_SV_LANG_YUE, SPT_SV_LANG_JA, SPT_SV_LANG_KO = range(6)
 SPT_PK_WEIGHTS_EMPTY = 1
 SPT_PK_TS_TOKEN, SPT_PK_TS_WORD, SPT_PK_TS_SEGMENT = 0, 1, 2
 SPT_MODEL_WEIGHTS_EXTERNAL = 1
@@ -160,6 +168,35 @@ class MsModelInfo(C.Structure):
 class MsTimings(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("stem_ms", "encoder_ms", "cross_kv_ms", "decode_ms", "total_ms")] + \
                [("n_steps", C.c_int32), ("batch", C.c_int32)]
+
+
+class SvModelParams(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("device", C.c_int32), ("max_batch", C.c_int32), ("max_samples", C.c_int32),
+                ("seed", C.c_uint64), ("ln_eps", C.c_float), ("sanm_shift", C.c_int32), ("lfr_m", C.c_int32),
+                ("lfr_n", C.c_int32), ("blank_id", C.c_int32), ("n_prefix", C.c_int32), ("lang_rows", C.c_int32 * 6),
+                ("event_row", C.c_int32), ("emo_row", C.c_int32), ("itn_row", C.c_int32), ("no_itn_row", C.c_int32)]
+
+
+class SvInferParams(C.Structure):
+    _fields_ = [("language", C.c_int32), ("use_itn", C.c_int32)]
+
+
+class SvResult(C.Structure):
+    _fields_ = [("text", C.c_char_p), ("tokens", C.POINTER(C.c_int32)), ("frames", C.POINTER(C.c_int32)),
+                ("top1", C.POINTER(C.c_float)), ("top2", C.POINTER(C.c_float)), ("n_tokens", C.c_int32),
+                ("prefix", C.c_int32 * 4)]
+
+
+class SvModelInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("d", "n_heads", "head_dim", "ff", "n_enc0_layers", "n_enc_layers",
+                                          "n_tp_layers", "n_vocab", "input_dim", "dtype", "max_batch",
+                                          "max_samples", "max_rows", "reserved")] + \
+               [("weight_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
+
+
+class SvTimings(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("frontend_ms", "encoder_ms", "ctc_ms", "total_ms")] + \
+               [("rows", C.c_int32), ("batch", C.c_int32)]
 
 
 class VadParams(C.Structure):
@@ -324,6 +361,40 @@ def load():
                "spt_moonshine_set_vocab", "spt_moonshine_transcribe", "spt_moonshine_transcribe_batch",
                "spt_moonshine_get_timings", "spt_moonshine_debug_stem", "spt_moonshine_debug_encode",
                "spt_moonshine_debug_logits"):
+        getattr(L, fn).restype = C.c_int
+    # SenseVoice
+    SR = C.POINTER(C.POINTER(SvResult))
+    svip = C.POINTER(SvInferParams)
+    L.spt_sensevoice_default_model_params.argtypes = [C.POINTER(SvModelParams)]
+    L.spt_sensevoice_default_model_params.restype = None
+    L.spt_sensevoice_default_infer_params.argtypes = [svip]
+    L.spt_sensevoice_default_infer_params.restype = None
+    L.spt_sensevoice_create.argtypes = [C.c_char_p, C.POINTER(SvModelParams), C.POINTER(vp), C.c_char_p, C.c_size_t]
+    L.spt_sensevoice_destroy.argtypes = [vp]
+    L.spt_sensevoice_destroy.restype = None
+    L.spt_sensevoice_last_error.argtypes = [vp]
+    L.spt_sensevoice_last_error.restype = C.c_char_p
+    L.spt_sensevoice_info.argtypes = [vp, C.POINTER(SvModelInfo)]
+    L.spt_sensevoice_tensor_numel.argtypes = [vp, C.c_char_p, C.POINTER(C.c_int64)]
+    L.spt_sensevoice_set_tensor.argtypes = [vp, C.c_char_p, fp, C.c_int64]
+    L.spt_sensevoice_missing_tensors.argtypes = [vp]
+    L.spt_sensevoice_missing_tensors.restype = C.c_int32
+    L.spt_sensevoice_set_cmvn.argtypes = [vp, fp, fp, C.c_int32]
+    L.spt_sensevoice_set_vocab.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int32]
+    L.spt_sensevoice_n_rows.argtypes = [vp, C.c_size_t]
+    L.spt_sensevoice_n_rows.restype = C.c_int32
+    L.spt_sensevoice_transcribe.argtypes = [vp, fp, C.c_size_t, svip, SR]
+    L.spt_sensevoice_transcribe_batch.argtypes = [vp, C.POINTER(fp), C.POINTER(C.c_size_t), C.c_size_t, svip, SR]
+    L.spt_sensevoice_result_free.argtypes = [C.POINTER(SvResult)]
+    L.spt_sensevoice_result_free.restype = None
+    L.spt_sensevoice_get_timings.argtypes = [vp, C.POINTER(SvTimings)]
+    L.spt_sensevoice_debug_features.argtypes = [vp, fp, C.c_size_t, fp]
+    L.spt_sensevoice_debug_encode.argtypes = [vp, fp, C.c_size_t, svip, fp]
+    L.spt_sensevoice_debug_frames.argtypes = [vp, fp, C.c_size_t, svip, i32p, fp, fp]
+    for fn in ("spt_sensevoice_create", "spt_sensevoice_info", "spt_sensevoice_tensor_numel", "spt_sensevoice_set_tensor",
+               "spt_sensevoice_set_cmvn", "spt_sensevoice_set_vocab", "spt_sensevoice_transcribe",
+               "spt_sensevoice_transcribe_batch", "spt_sensevoice_get_timings", "spt_sensevoice_debug_features",
+               "spt_sensevoice_debug_encode", "spt_sensevoice_debug_frames"):
         getattr(L, fn).restype = C.c_int
     for fn in EXPORTS:
         if fn.startswith("spt_parakeet_") and fn not in ("spt_parakeet_default_model_params",

@@ -348,7 +348,7 @@ spt_status run_windows(spt_ctx* c, std::vector<Window>& win, const float* const*
 
 extern "C" {
 
-const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine)"; }
+const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice)"; }
 
 const char* spt_language_code(int32_t lang_id) { return spt::lang_code(lang_id); }
 
