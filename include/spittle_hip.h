@@ -219,6 +219,11 @@ typedef struct {
 } spt_call_stats;
 
 spt_status spt_get_call_stats(const spt_ctx* ctx, spt_call_stats* s);
+/* Additive to ABI 14 (spt_call_stats' layout is unchanged): the last call's fused cross-Q +
+ * cross-attention launches (one per decoder layer of every one-token pass that took
+ * the fused path) and the engine calls it reran on the two-launch chain because a fused launch's
+ * bounded wait ran out (0 in normal operation).  Either pointer may be NULL. */
+spt_status spt_get_xq_stats(const spt_ctx* ctx, int32_t* fused_launches, int32_t* fallbacks);
 
 /* Multi-GPU load: the weight arena is one device allocation whose layout is a
  * pure function of (model, dtype), spt_model_info.weight_bytes long.  Rank 0 loads the model

@@ -212,6 +212,8 @@ extern "C" {
     pub fn spt_get_timings(ctx: *const spt_ctx, t: *mut spt_timings) -> spt_status;
     // ---- ABI 9: the whole last call (every window, fallback and beam step)
     pub fn spt_get_call_stats(ctx: *const spt_ctx, s: *mut spt_call_stats) -> spt_status;
+    // additive to ABI 14: fused cross-Q + cross-attention launches and chain reruns of the last call
+    pub fn spt_get_xq_stats(ctx: *const spt_ctx, fused_launches: *mut i32, fallbacks: *mut i32) -> spt_status;
 
     pub fn spt_weights_export(ctx: *mut spt_ctx, dev_dst: *mut c_void, bytes: usize) -> spt_status;
     pub fn spt_weights_import(ctx: *mut spt_ctx, dev_src: *const c_void, bytes: usize) -> spt_status;

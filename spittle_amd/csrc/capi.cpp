@@ -639,6 +639,14 @@ spt_status spt_get_call_stats(const spt_ctx* ctx, spt_call_stats* s) {
     return SPT_OK;
 }
 
+spt_status spt_get_xq_stats(const spt_ctx* ctx, int32_t* fused_launches, int32_t* fallbacks) {
+    if (!ctx) return SPT_ERR_INVALID_ARG;
+    const spt::CallStats& c = ctx->eng->call_stats();
+    if (fused_launches) *fused_launches = c.xq_fused;
+    if (fallbacks) *fallbacks = c.xq_fallbacks;
+    return SPT_OK;
+}
+
 spt_status spt_weights_export(spt_ctx* ctx, void* dev_dst, size_t bytes) {
     if (!ctx || !dev_dst) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
     try {

@@ -183,6 +183,31 @@ struct AttnWave {
             blk += NW;
         }
     }
+    // run()'s unrolled schedule in two halves, for a kernel whose queries arrive after its launch (the
+    // fused cross-Q + cross-attention): ring_fill issues the loads of the wave's first PF - 1 blocks,
+    // which need no query; ring_run then processes every block in run()'s order, loading the rest as
+    // run() does.  Only for cnt <= MAXB <= 8 (the launcher checks the key count).
+    template <int MAXB>
+    __device__ __forceinline__ void ring_fill(int blk, int nblk) {
+        static_assert(MAXB <= 8, "AttnWave: ring_fill / ring_run are the unrolled schedule");
+        const int cnt = blk < nblk ? (nblk - 1 - blk) / NW + 1 : 1;
+        const int mine = blk + (cnt - 1) * NW;
+#pragma unroll
+        for (int d = 0; d < PF - 1 && d < MAXB; ++d) load_blk(kc_[d], vc_[d], min(blk + d * NW, mine));
+    }
+    template <int MAXB>
+    __device__ __forceinline__ void ring_run(int blk, int nblk, const float (&qv)[NQ][8], const int (&lim)[NQ], int Tq) {
+        if (blk >= nblk) return;
+        const int cnt = (nblk - 1 - blk) / NW + 1;
+        const int mine = blk + (cnt - 1) * NW;
+#pragma unroll
+        for (int i = 0; i < MAXB; ++i) {
+            if (i >= cnt) break;
+            if (i + PF - 1 < MAXB)
+                load_blk(kc_[(i + PF - 1) % PF], vc_[(i + PF - 1) % PF], min(blk + (i + PF - 1) * NW, mine));
+            process(kc_[i % PF], vc_[i % PF], (blk + i * NW) * KB, qv, lim, Tq);
+        }
+    }
     // sum l and o over the 8 key slots of the wave (m is wave-uniform) into LDS
     __device__ __forceinline__ void to_lds(float (*s_m)[NQ], float (*s_l)[NQ], float (*s_o)[NQ][64], int wid,
                                            int lane) {

@@ -104,6 +104,7 @@ Engine::Engine(const ModelDims& dm, int dtype, int device, int max_batch, uint64
     // fewer slabs) is fixed per engine too; the pending-slab count a LayerNorm prologue sums is
     // a kernel template constant.
     select();
+    HIP_CHECK(hipDeviceGetAttribute(&n_cu_, hipDeviceAttributeMultiprocessorCount, dev_));
     HIP_CHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
     ev_.resize(12);  // 0-1 mel, 2-5 window / encoder / cross K/V, 6-7 decode, 8-9 a beam step, 10-11 H2D
     for (auto& e : ev_) HIP_CHECK(hipEventCreate(&e));
@@ -148,7 +149,7 @@ void Engine::release() {
     if (st_) (void)hipStreamSynchronize(st_);
     for (auto& g : groups_) {
         if (g.st) (void)hipStreamSynchronize(g.st);
-        for (auto& kv : g.graphs) (void)hipGraphExecDestroy(kv.second);
+        for (auto& kv : g.graphs) (void)hipGraphExecDestroy(kv.second.exec);
         if (g.ev) (void)hipEventDestroy(g.ev);
         if (g.st) (void)hipStreamDestroy(g.st);
     }
@@ -581,6 +582,7 @@ void Engine::alloc_workspace() {
         suppress_ = (uint32_t*)c.take((V / 32 + 1) * 4);
         suppress_lang_ = (uint32_t*)c.take((V / 32 + 1) * 4);
         scratch_ = (double*)c.take(64);
+        xq_err_ = (unsigned*)c.take(64);
         for (DecGroup& g : groups_) {  // each group sized for the whole batch (groups are re-sliced per call)
             g.dx = (float*)c.take(R * d * 4);
             g.dq = A(R * d);
@@ -613,6 +615,7 @@ void Engine::alloc_workspace() {
             g.cand_lp = (float*)c.take(B * 8 * 4);
             g.beam_tid = (int*)c.take(B * 4);
             g.kvrow = (int*)c.take(B * 4);
+            g.xq_gran = (unsigned long long*)c.take(16 * d * 8);
         }
         zero_ = (float*)c.take(R * d * 4);  // never written: the "no pending slab" operand
         if (!pass) {
@@ -940,6 +943,16 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
     const int xs = vw ? (vw_merge ? 1 : 8) : mapped ? 1 : xsplit_;
     const int ks = esz_ == 2 ? 128 : 64;
     hipStream_t st = g.st;
+    // LN2 + cross-Q and the cross-attention in one launch: one-token passes on the unsplit
+    // 8-wave path with identity windows whose workgroups are all resident at once; bitwise the two launches
+    const bool fuse = xq_on_ && probe_kind_ < 0 && Tq == 1 && !vw && !mapped && xs == 1 && dm_.n_dec <= 64 &&
+                      dec_xq_fused_ok(dt_, B, d, H, T, n_cu_);
+    xq_enq_ = fuse ? dm_.n_dec : 0;
+    if (fuse) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        HIP_CHECK(hipStreamIsCapturing(st, &cap));
+        if (cap == hipStreamCaptureStatusNone) cs_.xq_fused += xq_enq_;
+    }
     float* xc = g.dx;   // current residual rows (dec_embed / dec_finalize wrote this pass's input here)
     float* xo = g.dx2;  // the other buffer
     int np = 0;         // pending slabs in g.pend
@@ -991,11 +1004,19 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
         a = GemvArgs{};
         ln_input(a); a.lda = d; a.ln_w = e.ln2_w; a.ln_b = e.ln2_b; a.R = R;
         a.W = e.cq_w; a.N = d; a.K = d; a.bias = e.cq_b; a.C = g.dq; a.ldc = d;
-        gemv(dt_, GV_BIAS, A_LN, a, st);
+        if (fuse) {
+            if (np != 0) throw std::runtime_error("fused cross-Q launch: pending slabs before LN2");
+            XqFuseArgs x{};
+            x.kv = ckv_l; x.B_layout = E; x.H = H; x.T_enc = T; x.out = g.dao; x.gran = g.xq_gran; x.ds = g.ds;
+            x.err = xq_err_; x.layer = l;
+            dec_xq_fused(dt_, a, x, B, st);
+        } else {
+            gemv(dt_, GV_BIAS, A_LN, a, st);
+        }
         consumed();
         pmark(0, l, 0);
-        if (vw)
-        {
+        if (fuse) {  // the attention ran in the cross-Q launch
+        } else if (vw) {
             dec_cross_attn_vw(dt_, g.dq, ckv_l, B, E, H, T, Tq, g.xpart, st, mapped ? g.kvrow : nullptr,
                               mapped ? g.share : 1, per_query);
             if (vw_merge) dec_attn_part_merge(dt_, g.xpart, R, H, g.dao, st);
@@ -1238,6 +1259,13 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
         }
         DecodeRequest dq;  // no forcing, no blank rule, EOT irrelevant; the fast head
         dq.flags = 4u;
+        const bool xq_on = xq_on_;
+        xq_on_ = false;  // its result is read mid-call, before the call's fallback check: the two launches
+        struct XqRestore {
+            bool& on;
+            bool v;
+            ~XqRestore() { on = v; }
+        } xq_restore{xq_on_, xq_on};
         for (DecGroup* g : act) {
             reset_outputs(*g);
             upload_tokens(*g, [&](int, int) { return sp.sot; }, 1);
@@ -1317,12 +1345,13 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
                 if (e != hipSuccess) throw HipError(std::string("pass failed: ") + hipGetErrorString(e));
             }
     } else if (rq.n_steps > 1) {
-        std::vector<hipGraphExec_t> ex;
+        std::vector<PassGraph> ex;
         for (DecGroup* g : act) {
             // E and b0 are baked into the captured cross-K/V addresses, the window map's share
             // into the cross-attention grid (the map itself is read from g->kvrow)
             GraphKey key{g->B, E, g->b0, out_cap, rq.n_forced, rq.flags, rq.full};
             key.share = S;
+            key.fuse = xq_on_;
             auto it = g->graphs.find(key);
             if (it == g->graphs.end()) {
                 hipGraph_t graph;
@@ -1332,14 +1361,17 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
                 hipGraphExec_t exec;
                 HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
                 HIP_CHECK(hipGraphDestroy(graph));
-                it = g->graphs.emplace(key, exec).first;
+                it = g->graphs.emplace(key, PassGraph{exec, xq_enq_}).first;
             }
             ex.push_back(it->second);
         }
         const bool early_exit = !(rq.flags & 4u);
         std::vector<int> hdone(B);
         for (int s = 1; s < rq.n_steps; ++s) {
-            for (size_t i = 0; i < act.size(); ++i) HIP_CHECK(hipGraphLaunch(ex[i], act[i]->st));
+            for (size_t i = 0; i < act.size(); ++i) {
+                HIP_CHECK(hipGraphLaunch(ex[i].exec, act[i]->st));
+                cs_.xq_fused += ex[i].fused;
+            }
             ++passes;
             if (early_exit && (s % 16) == 0) {
                 bool all = true;
@@ -1370,11 +1402,38 @@ void Engine::decode(int B, const DecodeRequest& rq, int* tokens, float* top1, fl
                     int* ts_state_out) {
     select();
     require_weights();
+    // SPT_XQ_FUSE=0: the two-launch chain everywhere (read per call, applied when a pass is captured).  A
+    // beam search continues from the host step by step with no such check: it stays on the chain.
+    const char* xq_env = getenv("SPT_XQ_FUSE");
+    xq_on_ = rq.beam_k == 0 && !(xq_env && atoi(xq_env) == 0);
+    struct XqOff {
+        bool& on;
+        ~XqOff() { on = false; }
+    } xq_off{xq_on_};
+    const int fused0 = cs_.xq_fused;
     HIP_CHECK(hipEventRecord(ev_[6], st_));  // the decode groups wait for the encoded windows here
     run_decode(B, rq, tokens, top1, top2, lang_out, ts_state_out);
     HIP_CHECK(hipEventRecord(ev_[7], st_));
     HIP_CHECK(hipStreamSynchronize(st_));
     HIP_CHECK(hipGetLastError());
+    if (cs_.xq_fused > fused0) {
+        // a consumer of a fused launch that gave up waiting for its q (kXqTimeoutTicks) set the error
+        // word and left its output unwritten: the call's results are void.  Rerun it on the two launches.
+        // SPT_XQ_FUSE_FORCE_FALLBACK=1 takes this path after a normal call (tests).
+        unsigned err = 0;
+        HIP_CHECK(hipMemcpy(&err, xq_err_, 4, hipMemcpyDeviceToHost));
+        const char* force = getenv("SPT_XQ_FUSE_FORCE_FALLBACK");
+        if (err || (force && atoi(force) != 0)) {
+            HIP_CHECK(hipMemset(xq_err_, 0, 4));
+            xq_on_ = false;
+            cs_.xq_fallbacks++;
+            HIP_CHECK(hipEventRecord(ev_[6], st_));
+            run_decode(B, rq, tokens, top1, top2, lang_out, ts_state_out);
+            HIP_CHECK(hipEventRecord(ev_[7], st_));
+            HIP_CHECK(hipStreamSynchronize(st_));
+            HIP_CHECK(hipGetLastError());
+        }
+    }
     tm_.batch = B;
     cs_.engine_calls++;
     cs_.decoder_passes += tm_.n_decode_passes;
@@ -1548,9 +1607,9 @@ void Engine::beam_next(const int* src, const int* tokens, const int* rowstate, i
             hipGraphExec_t exec;
             HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
             HIP_CHECK(hipGraphDestroy(graph));
-            it = g.graphs.emplace(key, exec).first;
+            it = g.graphs.emplace(key, PassGraph{exec, 0}).first;
         }
-        HIP_CHECK(hipGraphLaunch(it->second, g.st));
+        HIP_CHECK(hipGraphLaunch(it->second.exec, g.st));
     }
     HIP_CHECK(hipEventRecord(ev_[9], g.st));
     read_cands(B, out);  // synchronises g.st

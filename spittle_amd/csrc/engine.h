@@ -67,6 +67,8 @@ struct CallStats {
     int engine_calls = 0, decoder_passes = 0, beam_steps = 0, encoder_windows = 0;
     int pd_passes = 0;     // ABI 12 counters of the persistent decoder pass (deleted in round 6): always 0
     int pd_fallbacks = 0;
+    int xq_fused = 0;      // fused cross-Q + cross-attention launches (dec_xq_fused) the call ran
+    int xq_fallbacks = 0;  // engine calls rerun on the two-launch chain after a consumer gave up waiting
     double device_ms = 0, encoder_ms = 0, decode_ms = 0;
 };
 
@@ -151,8 +153,10 @@ private:
         uint32_t flags;
         bool full;
         int share = 0;  // rows per window (0: identity rows, no window map)
+        bool fuse = false;  // captured while the fused cross-Q + cross-attention launch was allowed (xq_on_)
         bool operator<(const GraphKey& o) const {
             if (full != o.full) return full < o.full;
+            if (fuse != o.fuse) return fuse < o.fuse;
             if (B != o.B) return B < o.B;
             if (share != o.share) return share < o.share;
             if (B_total != o.B_total) return B_total < o.B_total;
@@ -161,6 +165,10 @@ private:
             if (n_forced != o.n_forced) return n_forced < o.n_forced;
             return flags < o.flags;
         }
+    };
+    struct PassGraph {
+        hipGraphExec_t exec;
+        int fused;  // dec_xq_fused launches in one replay
     };
     // An independent slice of the batch decoded on its own stream: its kernels fill
     // the launch gaps of the other group's latency-bound decoder chain.
@@ -189,7 +197,8 @@ private:
         float* cand_lp = nullptr;
         int* kvrow = nullptr;         // [B] encoded window of each row (window map)
         int share = 0;                // rows per window of this call (0: identity, no map)
-        std::map<GraphKey, hipGraphExec_t> graphs;
+        unsigned long long* xq_gran = nullptr;  // [16][d] q granules of the fused cross-Q + cross-attention launch
+        std::map<GraphKey, PassGraph> graphs;
         std::vector<int> host_tok;    // host sources of the call's token uploads
         size_t host_used = 0;
     };
@@ -230,6 +239,15 @@ private:
     bool pend_fold_ = true;
     // the LayerNorm source over the residual xc and np pending slabs at pend (slab stride `slab`)
     void ln_source(GemvArgs& a, float* xc, float* pend, int np, int64_t slab) const;
+    // The fused cross-Q + cross-attention launch (dec_xq_fused).  xq_on_: allowed for the
+    // passes being enqueued (decode() sets it for a non-beam call unless SPT_XQ_FUSE=0, and clears it for
+    // the rerun after a fallback); enqueue_layers then fuses the passes whose shape is eligible and
+    // leaves their launch count in xq_enq_ (added to the call's statistics at once when eager, per
+    // replay when captured).  xq_err_: the device word a consumer sets when it gives up waiting.
+    bool xq_on_ = false;
+    int xq_enq_ = 0;
+    int n_cu_ = 0;
+    unsigned* xq_err_ = nullptr;
     int xsplit_ = 1;  // cross-attention key chunks per (b, h) (merged by the output projection)
     int n_groups_ = 1;
     int max_rows_ = 64;  // decoder rows per pass (gemv_max_image_rows); larger batches use more groups  // SPT_DECODE_GROUPS=2 splits the batch over two streams

@@ -138,8 +138,13 @@ constexpr int attn_s(int asrc) { return asrc - 32; }
             a.stamp[2 * (blockIdx.x + blockIdx.y * gridDim.x) + (i)] = __builtin_amdgcn_s_memrealtime(); \
     } while (0)
 
-template <typename T, int MODE, int ASRC, int RG, int NWV, int CT, int MAXJ, bool EXACT = false>
-__global__ __launch_bounds__(64 * NWV) void gemv_kernel(GemvArgs a) {
+// The body is a device function so that the fused cross-Q + cross-attention launch (xq_fused_kernel)
+// runs the stand-alone kernel's instructions in its producer workgroups.  PUB (GV_BIAS only): each
+// output element is also published to the launch's consumers as an 8-byte granule {tag, the
+// element's stored bits} at gran[row * N + n], one relaxed agent-scope (write-through) store.
+template <typename T, int MODE, int ASRC, int RG, int NWV, int CT, int MAXJ, bool EXACT = false, bool PUB = false>
+__device__ __forceinline__ void gemv_body(const GemvArgs& a, unsigned long long* gran = nullptr, unsigned tag = 0) {
+    static_assert(!PUB || (MODE == GV_BIAS && sizeof(T) == 2), "gemv: granules carry one 16-bit GV_BIAS element");
     GV_STAMP(0);
     constexpr int KS = GV<T>::KS;
     constexpr int CPE = 16 / sizeof(T);  // elements per 16-byte chunk
@@ -446,7 +451,14 @@ __global__ __launch_bounds__(64 * NWV) void gemv_kernel(GemvArgs a) {
             if (row >= a.R) continue;
             const float y = acc[g][r] + bv;
             if constexpr (MODE == GV_BIAS) {
-                ((T*)a.C)[(size_t)row * a.ldc + n] = from_f<T>(y);
+                const T yt = from_f<T>(y);
+                ((T*)a.C)[(size_t)row * a.ldc + n] = yt;
+                if constexpr (PUB) {
+                    unsigned short bits;
+                    __builtin_memcpy(&bits, &yt, 2);
+                    __hip_atomic_store(gran + (size_t)row * a.N + n, ((unsigned long long)tag << 32) | bits,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
             } else if constexpr (MODE == GV_BIAS_GELU) {
                 ((T*)a.C)[(size_t)row * a.ldc + n] = from_f<T>(gelu_tanh(y));
             } else if constexpr (MODE == GV_PARTIAL) {
@@ -470,6 +482,11 @@ __global__ __launch_bounds__(64 * NWV) void gemv_kernel(GemvArgs a) {
         }
     }
     GV_STAMP(1);
+}
+
+template <typename T, int MODE, int ASRC, int RG, int NWV, int CT, int MAXJ, bool EXACT = false>
+__global__ __launch_bounds__(64 * NWV) void gemv_kernel(GemvArgs a) {
+    gemv_body<T, MODE, ASRC, RG, NWV, CT, MAXJ, EXACT>(a);
 }
 
 template <typename T, int MODE, int ASRC, int RG, int NWV, int CT, int MAXJ, bool EXACT = false>
@@ -673,8 +690,9 @@ __global__ __launch_bounds__(64 * AW) void self_attn_kernel(const T* __restrict_
 // or at the layer (kvrow: the window of each run of `share` rows).  A workgroup takes queries
 // [blockIdx.y * NQ, + NQ) of its run's share * Tq query rows (rows j * share .. + share - 1, Tq
 // each), so the decoders of one utterance (beam / best_of) read its window's K/V once per chunk.
-// (A fused LayerNorm + cross-Q projection prologue and key-chunk splits were measured slower on
-// MI355X: r1 exp_fused_xattn_pending_slabs.txt.)
+// (A fused LayerNorm + cross-Q projection prologue, every workgroup projecting its own q, and key-chunk
+// splits were measured slower on MI355X: r1 exp_fused_xattn_pending_slabs.txt.  xq_fused_kernel below
+// fuses the two launches with the projection done once.)
 template <typename T, int NQ, bool SPLIT, int NW = AW, int NIX = 0, int PF = 2>
 __global__ __launch_bounds__(64 * NW) void cross_attn_kernel(const T* __restrict__ q, const T* __restrict__ kv,
                                                              int B_layout, int H, int T_enc, int Tq,
@@ -727,6 +745,107 @@ __global__ __launch_bounds__(64 * NW) void cross_attn_kernel(const T* __restrict
         } else {
             out[(qrow0 + t) * (H * 64) + h * 64 + e] = from_f<T>(O / L);
         }
+    }
+}
+
+// LN2 + cross-Q projection and the one-row cross-attention in one launch.  The cross
+// K/V of a layer depend on nothing in the pass; only q does.  Workgroups [0, N / 16) are the cross-Q
+// GEMV's, unchanged (gemv_body, 10 exact waves), and publish each q element as a tagged granule
+// beside the q row they store; the following B x H workgroups are cross_attn_kernel<T, 1, false, 8>'s:
+// waves 0..7 put their first PF - 1 key blocks in flight at once, wave 8 sweeps the head's 64 granules
+// (one relaxed agent-scope 8-byte load per lane, s_sleep between sweeps) until every tag is this
+// pass's, and hands the bits over in LDS, so the attention waves' wait for q is a barrier, not a
+// load behind their K/V stream.  Producers wait on nothing and have the lowest workgroup indices;
+// the launcher admits the grid only if every workgroup is resident at once (> 128 VGPRs at 10 waves:
+// one workgroup per CU).  The wait is bounded by the wall clock (XqFuseArgs).
+// PF = 3: the deepest ring without scratch at this workgroup's 168 VGPRs per wave (4 spills: 20 / 36 bytes
+// per lane for bf16 / f16)
+// TOUCH: beside the ring, each attention wave also pulls the cache lines of its next TOUCH key blocks
+// towards L2 while it waits for q, one dword per line (a block of one wave is 32 K rows + 32 V rows of
+// 128 bytes: one line per lane, one load instruction, one register); the ring's own loads of those
+// blocks, issued once q is there, then find the lines in flight or in L2.
+template <typename T, int TOUCH, int PF = 3>
+__global__ __launch_bounds__(640) void xq_fused_kernel(GemvArgs a, XqFuseArgs x) {
+    const int n_prod = a.N / 16;
+    // a vector load: a scalar one would hold every workgroup's first kernel-argument wait for its round trip
+    const unsigned tag =
+        (__hip_atomic_load(&x.ds->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + 1u) * 64u + (unsigned)x.layer;
+    if ((int)blockIdx.x < n_prod) {
+        gemv_body<T, GV_BIAS, LN_SRC(0), 1, 10, 1, 1, true, true>(a, x.gran, tag);
+        return;
+    }
+    typedef AttnWave<T, 1, 0, AW, PF> W;
+    constexpr int MAXB = (1500 / W::KB + 1 + AW - 1) / AW;
+    // LDS carved from the dynamic region the producers size (statics would shift its base)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float (*s_o)[1][64] = (float (*)[1][64])smem;
+    float (*s_m)[1] = (float (*)[1])(smem + AW * 256);
+    float (*s_l)[1] = (float (*)[1])(smem + AW * 256 + AW * 4);
+    unsigned short* s_q = (unsigned short*)(smem + AW * 256 + AW * 8);  // the head's 64 q elements (bits)
+    int* s_ok = (int*)(smem + AW * 256 + AW * 8 + 128);
+    const int cb = (int)blockIdx.x - n_prod, j = cb / x.H, h = cb - j * x.H;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, g = lane & 7;
+    if (wid > AW) return;  // the producer geometry's tenth wave has no part here
+    const int nblk = cdiv(x.T_enc, W::KB);
+    W aw;
+    unsigned touch[TOUCH > 0 ? TOUCH : 1] = {};
+    if (wid < AW) {
+        const size_t kvo = ((size_t)j * x.H + h) * 4096 + 8 * g;
+        aw.init((const T*)x.kv + kvo, (const T*)x.kv + kvo + 2048, x.T_enc, lane, (int64_t)x.B_layout * x.H * 4096);
+        aw.template ring_fill<MAXB>(wid, nblk);
+        if constexpr (TOUCH > 0) {
+            const T* base = (const T*)x.kv + ((size_t)j * x.H + h) * 4096 + (lane < 32 ? 0 : 2048);
+#pragma unroll
+            for (int t = 0; t < TOUCH; ++t) {
+                const int key = min((wid + (PF - 1 + t) * AW) * W::KB + (lane & 31), x.T_enc - 1);
+                touch[t] = *(const unsigned*)(base + (uint32_t)((key >> 5) * aw.bstride + (key & 31) * 64));
+            }
+        }
+    } else {
+        unsigned long long* gp = x.gran + ((size_t)j * x.H + h) * 64 + lane;
+        bool ok = false;
+        if (__hip_atomic_load(x.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+            const long long t0 = wall_clock64();
+            for (;;) {
+                const unsigned long long v = __hip_atomic_load(gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (__all((unsigned)(v >> 32) == tag)) {
+                    s_q[lane] = (unsigned short)v;
+                    ok = true;
+                    break;
+                }
+                if (wall_clock64() - t0 > kXqTimeoutTicks) break;
+                __builtin_amdgcn_s_sleep(2);
+            }
+        }
+        if (lane == 0) {
+            *s_ok = ok ? 1 : 0;
+            if (!ok) __hip_atomic_store(x.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (wid >= AW || !*s_ok) return;
+    float qv[1][8];
+    int lim[1] = {x.T_enc};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        T qt;
+        __builtin_memcpy(&qt, &s_q[8 * g + e], 2);
+        qv[0][e] = to_f<T>(qt) * kLog2Scale;
+    }
+    aw.template ring_run<MAXB>(wid, nblk, qv, lim, 1);
+    aw.to_lds(s_m, s_l, s_o, wid, lane);
+    __syncthreads();
+    if (tid < 64) {
+        float M, L, O;
+        attn_merge<1, AW>(s_m, s_l, s_o, 0, tid, M, L, O);
+        ((T*)x.out)[((size_t)j * x.H + h) * 64 + tid] = from_f<T>(O / L);
+    }
+    if constexpr (TOUCH > 0) {
+        // the touched dwords are used nowhere; this keeps their loads (layer is never negative)
+        unsigned u = 0;
+#pragma unroll
+        for (int t = 0; t < TOUCH; ++t) u ^= touch[t];
+        if (x.layer < 0 && u == 0x9e3779b9u) __hip_atomic_store(x.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -823,6 +942,7 @@ __global__ __launch_bounds__(FIN_T) void finalize_kernel(FinalizeArgs a) {
     __shared__ int s_tok;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int step = a.ds->step, pos0 = a.ds->pos0;
+    const unsigned epoch = a.ds->epoch;
     TopP t{-INFINITY, 0x7fffffff, -INFINITY, 0};
     const TopP* p = (const TopP*)a.part + (size_t)b * a.n_tiles;
     for (int i = tid; i < a.n_tiles; i += FIN_T) t = top_merge(t, p[i]);
@@ -871,12 +991,16 @@ __global__ __launch_bounds__(FIN_T) void finalize_kernel(FinalizeArgs a) {
         if (prev == (unsigned)gridDim.x - 1) {
             a.ds->pos0 = pos0 + a.Tq;
             a.ds->step = step + 1;
+            a.ds->epoch = epoch + 1u;
             __hip_atomic_store(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
 
-__global__ void advance_kernel(DecState* ds, int n) { ds->pos0 += n; }
+__global__ void advance_kernel(DecState* ds, int n) {
+    ds->pos0 += n;
+    ds->epoch += 1u;
+}
 
 __global__ void reset_kernel(DecState* ds, unsigned* arrive) {
     ds->pos0 = 0;
@@ -1037,6 +1161,39 @@ void dec_cross_attn_vw(int dtype, const void* q, const void* kv, int B, int B_la
 #undef SPT_XV_T
 #undef SPT_XV_PF
 #undef SPT_XV
+    SPT_LAUNCH_CHECK();
+}
+
+bool dec_xq_fused_ok(int dtype, int B, int d, int H, int T_enc, int n_cu) {
+    // the chain's cross-Q must be the exact 10-wave GEMV (GV_EXACT_LN=0 gives it another K order)
+    static const bool exact_ln = !getenv("GV_EXACT_LN") || atoi(getenv("GV_EXACT_LN")) != 0;
+    return exact_ln && dtype_size(dtype) == 2 && d == 10 * GV<bf16>::KS && H * 64 == d && B >= 1 && B <= 16 &&
+           T_enc >= 256 && cdiv(T_enc, 32) <= 48 && d / 16 + B * H <= n_cu;
+}
+
+void dec_xq_fused(int dtype, const GemvArgs& cq, const XqFuseArgs& x, int B, hipStream_t st) {
+    if (dtype_size(dtype) != 2 || cq.R != B || B < 1 || B > 16 || cq.N != x.H * 64 || cq.K != 10 * GV<bf16>::KS ||
+        cq.N % 16 || cq.n_pend != 0 || !cq.ln_w || !cq.ln_b || !cq.C || x.T_enc < 256 || cdiv(x.T_enc, 32) > 48 ||
+        x.layer < 0 || x.layer >= 64 || !x.kv || !x.out || !x.gran || !x.ds || !x.err)
+        throw std::runtime_error("dec_xq_fused: not the fused launch's shape");
+    for (int p = 0; p < 4; ++p)
+        if (!cq.pend[p]) throw std::runtime_error("dec_xq_fused: LayerNorm prologue needs 4 pending slabs (zero slab if none)");
+    if ((int64_t)cdiv(x.T_enc, 32) * x.B_layout * x.H * 4096 >= (int64_t)INT32_MAX)
+        throw std::runtime_error("dec_xq_fused: a layer's cross K/V exceeds 2^31 elements");
+    GemvArgs a = cq;
+    a.ksplit = 1;
+    const int lds = std::max(4096, gv_img_bytes(a.R, a.K, 2) + 10 * 64 * (int)sizeof(f32x4));
+    const dim3 grid(a.N / 16 + B * x.H), blk(640);
+    // SPT_XQ_TOUCH=0: no touched blocks beyond the ring (A/B; no result changes).  Default 2; touching all
+    // four remaining blocks measured as slow as the two launches (profiles/r7/exp_xq_fuse.txt)
+    static const bool touch = !getenv("SPT_XQ_TOUCH") || atoi(getenv("SPT_XQ_TOUCH")) != 0;
+    if (dtype == DT_BF16) {
+        if (touch) hipLaunchKernelGGL((xq_fused_kernel<bf16, 2>), grid, blk, lds, st, a, x);
+        else hipLaunchKernelGGL((xq_fused_kernel<bf16, 0>), grid, blk, lds, st, a, x);
+    } else {
+        if (touch) hipLaunchKernelGGL((xq_fused_kernel<f16, 2>), grid, blk, lds, st, a, x);
+        else hipLaunchKernelGGL((xq_fused_kernel<f16, 0>), grid, blk, lds, st, a, x);
+    }
     SPT_LAUNCH_CHECK();
 }
 

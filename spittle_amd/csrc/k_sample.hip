@@ -337,6 +337,7 @@ __global__ __launch_bounds__(TW) void finalize_ts_kernel(TsArgs a) {
     __syncthreads();
     const int tok = s_tok;
     const int pos0 = a.ds->pos0;
+    const unsigned epoch = a.ds->epoch;
     const int pn = min(pos0 + a.Tq, a.ctx - 1);
     const T* e = (const T*)a.emb + (size_t)tok * a.d;
     const float* pp = a.pos + (size_t)pn * a.d;
@@ -349,6 +350,7 @@ __global__ __launch_bounds__(TW) void finalize_ts_kernel(TsArgs a) {
         if (prev == (unsigned)gridDim.x - 1) {
             a.ds->pos0 = pos0 + a.Tq;
             a.ds->step = step + 1;
+            a.ds->epoch = epoch + 1u;
             __hip_atomic_store(a.arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }

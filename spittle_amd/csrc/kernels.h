@@ -130,6 +130,8 @@ void enc_attention(int dtype, const void* qkv, int B, int T, int H, void* out, h
 struct DecState {        // device-resident step state
     int pos0;            // position of the first token fed this pass
     int step;            // index of the token being produced
+    unsigned epoch;      // passes this state has ended (finalize / advance add one; dec_reset leaves it):
+                         // the in-launch hand-off tag of dec_xq_fused, unique per pass under graph replay
 };
 
 enum { GV_BIAS = 0, GV_BIAS_GELU = 1, GV_PARTIAL = 2, GV_QKV_CACHE = 3, GV_LOGITS = 4, GV_BIAS_RESID = 5 };
@@ -190,6 +192,27 @@ void dec_cross_attn(int dtype, const void* q, const void* kv, int B, int B_layou
 // workgroups per head instead of 8, each re-reading the window's K/V, mostly from L2)
 void dec_cross_attn_vw(int dtype, const void* q, const void* kv, int B, int B_layout, int H, int T_enc, int Tq,
                        float* part, hipStream_t st, const int* kvrow = nullptr, int share = 1, bool per_query = false);
+// LN2 + cross-Q projection and the one-row 8-wave cross-attention in ONE launch:
+// workgroups [0, N / 16) are the cross-Q GEMV's (cq: the GV_BIAS / A_LN arguments, no pending slabs),
+// the next B x H are the attention's, which start streaming their K/V at launch and take q, when it
+// arrives, from 8-byte granules {tag, bf16 / f16 bits} the producers publish (gran [R][N]; tag =
+// (ds->epoch + 1) * 64 + layer).  Bitwise the two launches' result.  A consumer that has waited
+// kXqTimeoutTicks of the 100 MHz wall clock sets *err and exits (the engine then reruns the call
+// on the two launches); one that finds *err set does not wait at all.
+struct XqFuseArgs {
+    const void* kv; int B_layout, H, T_enc;  // dec_cross_attn's kv (no window map), layout rows, heads, keys
+    void* out;                               // attention output [B][H * 64]
+    unsigned long long* gran;                // [B][H * 64] granules
+    const DecState* ds;
+    unsigned* err;
+    int layer;                               // < 64
+};
+constexpr long long kXqTimeoutTicks = 2000000;  // 20 ms against a hand-off of microseconds
+// whether the shapes are the fused launch's (host): 16-bit dtype, one query per row, the exact
+// 10-wave cross-Q geometry (K = 1280), 1500-key class windows, and every workgroup resident at once
+bool dec_xq_fused_ok(int dtype, int B, int d, int H, int T_enc, int n_cu);
+void dec_xq_fused(int dtype, const GemvArgs& cq, const XqFuseArgs& x, int B, hipStream_t st);
+
 // the 8 partials of each of R query rows x H heads merged into out [R][H * 64] (bitwise the 8-wave
 // kernel's output), for a plain (A_DIRECT) cross output projection
 void dec_attn_part_merge(int dtype, const float* part, int R, int H, void* out, hipStream_t st);

@@ -276,6 +276,14 @@ class WhisperEngine:
         self._check(self._lib.spt_get_call_stats(self._ctx, C.byref(t)))
         return {k: getattr(t, k) for k, _ in t._fields_ if k != "reserved0"}
 
+    def xq_stats(self) -> dict:
+        """The last call's fused cross-Q + cross-attention launches and the engine calls it reran on the
+        two-launch chain (spt_get_xq_stats)."""
+        self._need()
+        f, b = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.spt_get_xq_stats(self._ctx, C.byref(f), C.byref(b)))
+        return {"fused_launches": f.value, "fallbacks": b.value}
+
     def debug_mel(self, samples, seek: int = 0) -> np.ndarray:
         """The normalised log-mel [n_mels][3000] the encoder takes for the window at frame `seek`
         (frames seek .. seek + 2999 of the whole utterance's log-mel)."""
