@@ -291,6 +291,49 @@ spt_status spt_debug_ggml_tokenize(const char* model_path, const char* text, int
                                    int32_t* n_out);
 /* host-only: the host reference dequantisation of n elements of one ggml type to f32 */
 spt_status spt_debug_ggml_dequant(int32_t ggml_type, const void* src, int64_t n, float* dst);
+/* The sampler kernels alone (additive over ABI 14): whisper_full's token rules, the beam candidates
+ * and the beam K/V gather on caller-supplied arrays, with no context and no model, on a stream of
+ * their own on `device`.  Argument errors and the launchers' own (a vocabulary above 53248 tokens,
+ * k outside 1..8) return SPT_ERR_INVALID_ARG with the message in err; no device: SPT_ERR_DEVICE.
+ * spt_sample_params is one call's decoding parameters as the kernels read them. */
+typedef struct {
+    float temperature;       /* 0: greedy; > 0: a draw from softmax(logits / temperature) */
+    int32_t suppress_blank;  /* [eot] and the blank token masked at step 0 */
+    int32_t no_ts;           /* every timestamp masked */
+    int32_t max_initial;     /* step 0: timestamps above beg + max_initial masked; < 0: off */
+    int32_t n_max;           /* the repetition guard's step (n_max - 1) */
+    int32_t max_tokens;      /* > 0: the segment ends at this token index */
+    uint64_t seed;           /* of the (seed, row, step) draw stream */
+} spt_sample_params;
+/* n_steps decoder steps of the token path: for each step s the statistics launch and the
+ * finalize launch on logits [n_steps][B][ldl], as the engine enqueues them, so that the device's
+ * own token history feeds the next step's rules.  dtype is the embedding's (emb [n_vocab][d] f32 is
+ * rounded to it once; pos [ctx][d] stays f32).  suppress: (n_vocab + 31) / 32 bit words.  In and
+ * out (the caller's initial contents are uploaded, the final ones returned): state [B][4] = has_ts,
+ * seek_delta, result_len, status; done [B]; out_tok / out_plog / out_tid [B][out_cap]; dec_state =
+ * {pos0, step, epoch}.  forced [B][forced_len] may be NULL.  Out: next_tok [B], x [B][d] of the
+ * last step, *arrive the last-arriver counter (0 after a complete step). */
+spt_status spt_debug_sample_tokens(int32_t device, int32_t dtype, const float* logits, int32_t n_steps, int32_t B,
+                                   int32_t n_vocab, int32_t ldl, int32_t eot, int32_t beg, int32_t blank,
+                                   const uint32_t* suppress, const spt_sample_params* prm, const int32_t* seek,
+                                   const int32_t* seek_end, int32_t* state, int32_t* done, const int32_t* forced,
+                                   int32_t forced_len, int32_t out_cap, int32_t* dec_state, int32_t Tq, int32_t d,
+                                   int32_t ctx, const float* emb, const float* pos, int32_t* out_tok, float* out_plog,
+                                   float* out_tid, int32_t* next_tok, float* x, uint32_t* arrive, char* err,
+                                   size_t errlen);
+/* one beam candidate launch on logits [B][ldl]: row [B][4] = last token, previous token, has_ts,
+ * seek_delta; chunked != 0: the chunk + merge kernels, 0: the one-workgroup kernel.  cand_id /
+ * cand_lp [B][8] (in and out: the first k of each row are written), tid [B]. */
+spt_status spt_debug_sample_beam(int32_t device, const float* logits, int32_t B, int32_t n_vocab, int32_t ldl,
+                                 int32_t eot, int32_t beg, int32_t blank, const uint32_t* suppress,
+                                 const spt_sample_params* prm, const int32_t* row, int32_t step, int32_t k,
+                                 int32_t chunked, int32_t* cand_id, float* cand_lp, int32_t* tid, char* err,
+                                 size_t errlen);
+/* one beam K/V gather: src and dst [L][2][B][H][ctx][64] f32, converted to dtype for the launch
+ * and back; dst row b takes positions < pos0 of src row rows[b] and keeps the rest. */
+spt_status spt_debug_sample_kv_gather(int32_t device, int32_t dtype, const float* src, float* dst,
+                                      const int32_t* rows, int32_t L, int32_t B, int32_t H, int32_t ctx,
+                                      int32_t pos0, char* err, size_t errlen);
 
 /* ================================================================================================
  * ABI 6: Parakeet-V3 (NeMo FastConformer-TDT), the app's other local engine;

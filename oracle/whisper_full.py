@@ -11,8 +11,10 @@ Cargo.lock:8156-8174; not present here, so "parity unpinned" against whisper.cpp
   * whisper_sample_token (best): first maximum; plog; tid;
   * whisper_full_with_state: decoder bookkeeping (seek_delta, result_len, failure / completion),
     whisper_sequence_score, seek loop, prompt_past, segment assembly.
-Temperature sampling (fallback) draws from a device stream and is not restated; the window
-loop here runs greedy decoding at temperature 0 only (temperature_inc = 0).
+Temperature sampling (fallback) draws from a device stream; it is restated per token, with that
+stream, in tests/sampler_ref.py (sample, u01) and checked against the kernels alone by
+tests/test_gpu_sampler.py.  The window loop here runs greedy decoding at temperature 0 only
+(temperature_inc = 0).
 Each step recomputes the decoder over the whole token prefix (oracle.wo_decode_logits).  Every
 window's encoder input is frames [seek, seek + 3000) of ONE log-mel of the whole input
 (oracle.mel_full: whisper_pcm_to_mel's global max - 8 clamp), as whisper_full_with_state does.

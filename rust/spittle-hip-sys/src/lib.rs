@@ -130,6 +130,19 @@ pub struct spt_call_stats {
     pub pd_fallbacks: i32,
 }
 
+/// decoding parameters of the `spt_debug_sample_*` test hooks
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default)]
+pub struct spt_sample_params {
+    pub temperature: f32,
+    pub suppress_blank: i32,
+    pub no_ts: i32,
+    pub max_initial: i32,
+    pub n_max: i32,
+    pub max_tokens: i32,
+    pub seed: u64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default)]
 pub struct spt_timings {
@@ -261,6 +274,77 @@ extern "C" {
         n_out: *mut i32,
     ) -> spt_status;
     pub fn spt_debug_ggml_dequant(ggml_type: i32, src: *const c_void, n: i64, dst: *mut f32) -> spt_status;
+    // the sampler kernels alone (test hooks, additive over ABI 14)
+    pub fn spt_debug_sample_tokens(
+        device: i32,
+        dtype: i32,
+        logits: *const f32,
+        n_steps: i32,
+        b: i32,
+        n_vocab: i32,
+        ldl: i32,
+        eot: i32,
+        beg: i32,
+        blank: i32,
+        suppress: *const u32,
+        prm: *const spt_sample_params,
+        seek: *const i32,
+        seek_end: *const i32,
+        state: *mut i32,
+        done: *mut i32,
+        forced: *const i32,
+        forced_len: i32,
+        out_cap: i32,
+        dec_state: *mut i32,
+        tq: i32,
+        d: i32,
+        ctx: i32,
+        emb: *const f32,
+        pos: *const f32,
+        out_tok: *mut i32,
+        out_plog: *mut f32,
+        out_tid: *mut f32,
+        next_tok: *mut i32,
+        x: *mut f32,
+        arrive: *mut u32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_sample_beam(
+        device: i32,
+        logits: *const f32,
+        b: i32,
+        n_vocab: i32,
+        ldl: i32,
+        eot: i32,
+        beg: i32,
+        blank: i32,
+        suppress: *const u32,
+        prm: *const spt_sample_params,
+        row: *const i32,
+        step: i32,
+        k: i32,
+        chunked: i32,
+        cand_id: *mut i32,
+        cand_lp: *mut f32,
+        tid: *mut i32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_sample_kv_gather(
+        device: i32,
+        dtype: i32,
+        src: *const f32,
+        dst: *mut f32,
+        rows: *const i32,
+        l: i32,
+        b: i32,
+        h: i32,
+        ctx: i32,
+        pos0: i32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
 
     // ---- ABI 6: Parakeet-V3
     pub fn spt_parakeet_default_model_params(p: *mut spt_pk_model_params);

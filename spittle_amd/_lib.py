@@ -57,6 +57,8 @@ EXPORTS = [
     "spt_sensevoice_set_vocab", "spt_sensevoice_n_rows", "spt_sensevoice_transcribe",
     "spt_sensevoice_transcribe_batch", "spt_sensevoice_result_free", "spt_sensevoice_get_timings",
     "spt_sensevoice_debug_features", "spt_sensevoice_debug_encode", "spt_sensevoice_debug_frames",
+    # the sampler kernels alone (test hooks, additive over ABI 14)
+    "spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather",
 ]
 SPT_SV_LANG_AUTO, SPT_SV_LANG_ZH, SPT_SV_LANG_EN, SPT_SV_LANG_YUE, SPT_SV_LANG_JA, SPT_SV_LANG_KO = range(6)
 SPT_PK_WEIGHTS_EMPTY = 1
@@ -197,6 +199,11 @@ class SvModelInfo(C.Structure):
 class SvTimings(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("frontend_ms", "encoder_ms", "ctc_ms", "total_ms")] + \
                [("rows", C.c_int32), ("batch", C.c_int32)]
+
+
+class SampleParams(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("suppress_blank", C.c_int32), ("no_ts", C.c_int32),
+                ("max_initial", C.c_int32), ("n_max", C.c_int32), ("max_tokens", C.c_int32), ("seed", C.c_uint64)]
 
 
 class VadParams(C.Structure):
@@ -396,6 +403,16 @@ def load():
                "spt_sensevoice_set_cmvn", "spt_sensevoice_set_vocab", "spt_sensevoice_transcribe",
                "spt_sensevoice_transcribe_batch", "spt_sensevoice_get_timings", "spt_sensevoice_debug_features",
                "spt_sensevoice_debug_encode", "spt_sensevoice_debug_frames"):
+        getattr(L, fn).restype = C.c_int
+    # the sampler kernels alone
+    u32p, spp, i32 = C.POINTER(C.c_uint32), C.POINTER(SampleParams), C.c_int32
+    L.spt_debug_sample_tokens.argtypes = [i32, i32, fp, i32, i32, i32, i32, i32, i32, i32, u32p, spp, i32p, i32p, i32p,
+                                          i32p, i32p, i32, i32, i32p, i32, i32, i32, fp, fp, i32p, fp, fp, i32p, fp,
+                                          u32p, C.c_char_p, C.c_size_t]
+    L.spt_debug_sample_beam.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, u32p, spp, i32p, i32, i32, i32, i32p, fp,
+                                        i32p, C.c_char_p, C.c_size_t]
+    L.spt_debug_sample_kv_gather.argtypes = [i32, i32, fp, fp, i32p, i32, i32, i32, i32, i32, C.c_char_p, C.c_size_t]
+    for fn in ("spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather"):
         getattr(L, fn).restype = C.c_int
     for fn in EXPORTS:
         if fn.startswith("spt_parakeet_") and fn not in ("spt_parakeet_default_model_params",
