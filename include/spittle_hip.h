@@ -334,6 +334,37 @@ spt_status spt_debug_sample_beam(int32_t device, const float* logits, int32_t B,
 spt_status spt_debug_sample_kv_gather(int32_t device, int32_t dtype, const float* src, float* dst,
                                       const int32_t* rows, int32_t L, int32_t B, int32_t H, int32_t ctx,
                                       int32_t pos0, char* err, size_t errlen);
+/* The Whisper attention kernels alone (additive over ABI 14): one launch of the
+ * engine's launchers on caller-supplied host f32 arrays, rounded on the host to dtype (f32, bf16 or
+ * f16) and returned as f32, on a stream of their own on `device`.  The head dimension is 64.  A shape
+ * a launcher would refuse, or that would read outside a buffer, returns SPT_ERR_INVALID_ARG with the
+ * message in err before any launch; no device: SPT_ERR_DEVICE.
+ * Encoder: qkv [B*T][3*H*64] (q | k | v, head h at h*64) -> out [B*T][H*64]; the SPT_ATTN_* variant
+ * switches are read per launch, as the launcher reads them. */
+spt_status spt_debug_attn_enc(int32_t device, int32_t dtype, const float* qkv, int32_t B, int32_t T, int32_t H,
+                              float* out, char* err, size_t errlen);
+/* Decoder self-attention: q [B*Tq][H*64] (row b*Tq + t at position pos0 + t, keys 0..pos0 + t) over
+ * the whole cache [2][B][H][ctx][64] as given (rows from pos0 + Tq up are the caller's to poison)
+ * -> out [B*Tq][H*64].  Tq 1..4, pos0 >= 0, pos0 + Tq <= ctx. */
+spt_status spt_debug_attn_self(int32_t device, int32_t dtype, const float* q, const float* cache, int32_t B,
+                               int32_t H, int32_t ctx, int32_t Tq, int32_t pos0, float* out, char* err,
+                               size_t errlen);
+/* Decoder cross-attention: q [B*Tq][H*64]; k, v [B_layout][H][T_enc][64] are laid out as one layer of
+ * the cross K/V cache (32-key blocks, the keys from T_enc to the next multiple of 32 filled with
+ * pad_value).  Row b attends to window b0 + b, or with a window map kvrow [B] (required for share >
+ * 1) rows j*share .. + share - 1 to window b0 + kvrow[j*share].  splits 2..4 (8-wave mode only): the
+ * keys in that many chunks, partials instead of out.  mode: */
+enum {
+    SPT_ATTN_CROSS_8WAVE = 0,       /* out [B*Tq][H*64], or for splits > 1 part [B*Tq][H][splits][66] */
+    SPT_ATTN_CROSS_VW = 1,          /* one wave per workgroup: part [B*Tq][H][8][66] = {o[64], m, l} */
+    SPT_ATTN_CROSS_VW_PQ = 2,       /* the same with one query row per workgroup (Tq = 1) */
+    SPT_ATTN_CROSS_VW_MERGE = 3,    /* VW, then the partial merge launch: out */
+    SPT_ATTN_CROSS_VW_PQ_MERGE = 4  /* VW_PQ, then the partial merge launch: out */
+};
+spt_status spt_debug_attn_cross(int32_t device, int32_t dtype, int32_t mode, const float* q, const float* k,
+                                const float* v, float pad_value, int32_t B, int32_t B_layout, int32_t b0, int32_t H,
+                                int32_t T_enc, int32_t Tq, int32_t splits, const int32_t* kvrow, int32_t share,
+                                float* out, float* part, char* err, size_t errlen);
 
 /* ================================================================================================
  * ABI 6: Parakeet-V3 (NeMo FastConformer-TDT), the app's other local engine;

@@ -25,6 +25,12 @@ pub const SPT_DTYPE_BF16: spt_dtype = 1;
 pub const SPT_DTYPE_F16: spt_dtype = 2;
 /// ABI 13, `spt_pk_model_params.dtype` only: the int8 ONNX export's own arithmetic
 pub const SPT_DTYPE_I8: spt_dtype = 3;
+/// `mode` of `spt_debug_attn_cross`
+pub const SPT_ATTN_CROSS_8WAVE: i32 = 0;
+pub const SPT_ATTN_CROSS_VW: i32 = 1;
+pub const SPT_ATTN_CROSS_VW_PQ: i32 = 2;
+pub const SPT_ATTN_CROSS_VW_MERGE: i32 = 3;
+pub const SPT_ATTN_CROSS_VW_PQ_MERGE: i32 = 4;
 /// `spt_pk_act` of `spt_parakeet_debug_qgemm`
 pub const SPT_PK_ACT_NONE: i32 = 0;
 pub const SPT_PK_ACT_RELU: i32 = 1;
@@ -342,6 +348,54 @@ extern "C" {
         h: i32,
         ctx: i32,
         pos0: i32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    // the attention kernels alone (test hooks, additive over ABI 14); mode: SPT_ATTN_CROSS_*
+    pub fn spt_debug_attn_enc(
+        device: i32,
+        dtype: i32,
+        qkv: *const f32,
+        b: i32,
+        t: i32,
+        h: i32,
+        out: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_attn_self(
+        device: i32,
+        dtype: i32,
+        q: *const f32,
+        cache: *const f32,
+        b: i32,
+        h: i32,
+        ctx: i32,
+        tq: i32,
+        pos0: i32,
+        out: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_attn_cross(
+        device: i32,
+        dtype: i32,
+        mode: i32,
+        q: *const f32,
+        k: *const f32,
+        v: *const f32,
+        pad_value: f32,
+        b: i32,
+        b_layout: i32,
+        b0: i32,
+        h: i32,
+        t_enc: i32,
+        tq: i32,
+        splits: i32,
+        kvrow: *const i32,
+        share: i32,
+        out: *mut f32,
+        part: *mut f32,
         err: *mut c_char,
         errlen: usize,
     ) -> spt_status;

@@ -59,7 +59,10 @@ EXPORTS = [
     "spt_sensevoice_debug_features", "spt_sensevoice_debug_encode", "spt_sensevoice_debug_frames",
     # the sampler kernels alone (test hooks, additive over ABI 14)
     "spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather",
+    # the attention kernels alone (test hooks, additive over ABI 14)
+    "spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross",
 ]
+SPT_ATTN_CROSS_8WAVE, SPT_ATTN_CROSS_VW, SPT_ATTN_CROSS_VW_PQ, SPT_ATTN_CROSS_VW_MERGE, SPT_ATTN_CROSS_VW_PQ_MERGE = range(5)
 SPT_SV_LANG_AUTO, SPT_SV_LANG_ZH, SPT_SV_LANG_EN, SPT_SV_LANG_YUE, SPT_SV_LANG_JA, SPT_SV_LANG_KO = range(6)
 SPT_PK_WEIGHTS_EMPTY = 1
 SPT_PK_TS_TOKEN, SPT_PK_TS_WORD, SPT_PK_TS_SEGMENT = 0, 1, 2
@@ -413,6 +416,13 @@ def load():
                                         i32p, C.c_char_p, C.c_size_t]
     L.spt_debug_sample_kv_gather.argtypes = [i32, i32, fp, fp, i32p, i32, i32, i32, i32, i32, C.c_char_p, C.c_size_t]
     for fn in ("spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather"):
+        getattr(L, fn).restype = C.c_int
+    # the attention kernels alone
+    L.spt_debug_attn_enc.argtypes = [i32, i32, fp, i32, i32, i32, fp, C.c_char_p, C.c_size_t]
+    L.spt_debug_attn_self.argtypes = [i32, i32, fp, fp, i32, i32, i32, i32, i32, fp, C.c_char_p, C.c_size_t]
+    L.spt_debug_attn_cross.argtypes = [i32, i32, i32, fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32p,
+                                       i32, fp, fp, C.c_char_p, C.c_size_t]
+    for fn in ("spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross"):
         getattr(L, fn).restype = C.c_int
     for fn in EXPORTS:
         if fn.startswith("spt_parakeet_") and fn not in ("spt_parakeet_default_model_params",

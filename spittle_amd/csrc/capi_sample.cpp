@@ -11,70 +11,14 @@
 #include <vector>
 
 #include "../../include/spittle_hip.h"
+#include "capi_debug.h"
 #include "capi_internal.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace {
 
-void set_err(char* buf, size_t len, const std::string& m) {
-    if (buf && len) {
-        strncpy(buf, m.c_str(), len - 1);
-        buf[len - 1] = 0;
-    }
-}
-
-// the calling thread's device and a stream on it, with every buffer the call allocates
-struct Scope {
-    hipStream_t st = nullptr;
-    std::vector<void*> bufs;
-    explicit Scope(int device) {
-        HIP_CHECK(hipSetDevice(device));
-        HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    }
-    ~Scope() {
-        if (st) {
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamDestroy(st);
-        }
-        for (void* p : bufs) (void)hipFree(p);
-    }
-    template <typename T> T* alloc(size_t n) {
-        void* p = nullptr;
-        HIP_CHECK(hipMalloc(&p, (n ? n : 1) * sizeof(T)));
-        bufs.push_back(p);
-        return (T*)p;
-    }
-    template <typename T> T* up(const T* h, size_t n) {
-        T* p = alloc<T>(n);
-        HIP_CHECK(hipMemcpyAsync(p, h, n * sizeof(T), hipMemcpyHostToDevice, st));
-        return p;
-    }
-    template <typename T> void down(T* h, const T* dev, size_t n) {
-        HIP_CHECK(hipMemcpyAsync(h, dev, n * sizeof(T), hipMemcpyDeviceToHost, st));
-    }
-    void sync() { HIP_CHECK(hipStreamSynchronize(st)); }
-};
-
-spt_status device_ok(int32_t device, char* err, size_t errlen) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_err(err, errlen, "no HIP device available");
-        return SPT_ERR_DEVICE;
-    }
-    if (device < 0 || device >= ndev) {
-        set_err(err, errlen, "device ordinal out of range");
-        return SPT_ERR_INVALID_ARG;
-    }
-    return SPT_OK;
-}
-
-// f32 -> the storage of an engine dtype, on the host (round-to-nearest-even, the device's conversion)
-std::vector<uint16_t> to_half_storage(int dtype, const float* v, size_t n) {
-    std::vector<uint16_t> o(n);
-    for (size_t i = 0; i < n; ++i) o[i] = dtype == spt::DT_BF16 ? spt::f2bf(v[i]) : spt::f2h_bits(v[i]);
-    return o;
-}
+using namespace spt::dbg;
 
 void check_vocab(int32_t B, int32_t n_vocab, int32_t ldl, int32_t eot, int32_t beg, int32_t blank) {
     if (B < 1 || B > 1024) throw std::runtime_error("debug_sample: need 1..1024 rows");
