@@ -78,6 +78,17 @@ typedef struct {
 #define SPT_MODEL_WEIGHTS_EXTERNAL 1u  /* allocate the weight arena but do not generate / dequantise
                                           into it: spt_weights_import fills it (a multi-GPU load
                                           where rank 0 loads and RCCL broadcasts the arena) */
+#define SPT_MODEL_QUANT_RESIDENT 2u    /* SPT_HAS_QUANT_RESIDENT: a ggml file's decoder matrices (per layer
+                                          the fused q/k/v, both attention outputs, the cross query, fc1,
+                                          fc2) and its token embedding stay in HBM in their quantised
+                                          blocks and the decoder GEMVs dequantise them in registers; every
+                                          result is bit for bit that of the same file loaded without the
+                                          flag.  q4_1, q5_0 and q5_1 tensors are kept; a matrix of any other
+                                          type (or a fused one whose parts differ) is dequantised at load as
+                                          before, so K-quant and f16 files and synthetic models load with
+                                          nothing resident.  bf16 / f16 engines; SPT_DTYPE_F32:
+                                          SPT_ERR_UNSUPPORTED at create.  weight_bytes is the smaller arena;
+                                          export / import work between contexts of the same file and flag */
 
 typedef struct {
     const char* language;        /* ISO-639-1 ("en", "zh", ...); NULL or "auto" = auto-detect
@@ -365,6 +376,44 @@ spt_status spt_debug_attn_cross(int32_t device, int32_t dtype, int32_t mode, con
                                 const float* v, float pad_value, int32_t B, int32_t B_layout, int32_t b0, int32_t H,
                                 int32_t T_enc, int32_t Tq, int32_t splits, const int32_t* kvrow, int32_t share,
                                 float* out, float* part, char* err, size_t errlen);
+
+/* Quantised decoder weights resident in HBM (additive over ABI 14, announced by
+ * SPT_HAS_QUANT_RESIDENT).  spt_debug_qgemv is the decoder GEMV alone over one
+ * quantised matrix, with no context and no model, on a stream of its own on `device`: the launch
+ * runs twice, once on the weights expanded to dtype by the loader's dequantisation kernel and once
+ * on the matrix packed in its blocks and dequantised in registers, and both results come back as f32.
+ *   ggml_type   SPT_GGML_Q4_1, _Q5_0 or _Q5_1 (every other type: SPT_ERR_UNSUPPORTED)
+ *   blocks      the file's blocks of W [N][K / 32], blocks_bytes of them (must be the tensor's size)
+ *   dtype       SPT_DTYPE_BF16 or SPT_DTYPE_F16 (SPT_DTYPE_F32: SPT_ERR_UNSUPPORTED)
+ *   act         f32 [R][K]: SPT_QGEMV_A_DIRECT rounds it to dtype as the activation rows; SPT_QGEMV_A_LN
+ *               takes it as the f32 residual rows of the fused LayerNorm (ln_w, ln_b [K]; K <= 1536)
+ *   bias [N] (or NULL), resid [R][N] (SPT_GV_BIAS_RESID: required, the rows the product is added to;
+ *               SPT_GV_PARTIAL: optional, added into slab 0)
+ *   (mode, a_src) one of the decoder's pairs: (BIAS | BIAS_GELU | QKV_CACHE | LOGITS, A_LN),
+ *               (PARTIAL | BIAS_RESID, A_DIRECT); ksplit > 1 with SPT_GV_PARTIAL only
+ *   out_plain / out_packed   [R][N]; SPT_GV_PARTIAL: [ksplit][R][N]; SPT_GV_QKV_CACHE (N = 3 d, d a
+ *               multiple of 64, one token per row at position 0): [R][3 d] = q | the appended k | v
+ *   top_plain / top_packed   SPT_GV_LOGITS only: the top-2 partials [R][ceil(N / 16)][4] as stored
+ *               (16 bytes each: f32 best, i32 index, f32 runner-up, 0); no token is suppressed
+ *   unpacked    optional [N][K]: the packed matrix dequantised back on the host.  It is written before
+ *               the device is looked for, so a valid call without a device fills it and returns
+ *               SPT_ERR_DEVICE.
+ * K must be a multiple of 128, R in 1..64, N >= 1.  Every argument error, and every shape the
+ * launcher would refuse, returns SPT_ERR_INVALID_ARG with the message in err before any launch. */
+#define SPT_HAS_QUANT_RESIDENT 1
+/* what SPT_MODEL_QUANT_RESIDENT kept: the count of weights held quantised, their bytes in the arena
+ * (padding included) and their ggml type (-1: none, or matrices of several types).  Any pointer may be NULL. */
+spt_status spt_get_weight_residency(const spt_ctx* ctx, int64_t* resident_weights, int64_t* resident_bytes,
+                                    int32_t* ggml_type);
+enum { SPT_GGML_Q4_1 = 3, SPT_GGML_Q5_0 = 6, SPT_GGML_Q5_1 = 7 };
+enum { SPT_GV_BIAS = 0, SPT_GV_BIAS_GELU = 1, SPT_GV_PARTIAL = 2, SPT_GV_QKV_CACHE = 3, SPT_GV_LOGITS = 4,
+       SPT_GV_BIAS_RESID = 5 };
+enum { SPT_QGEMV_A_DIRECT = 0, SPT_QGEMV_A_LN = 1 };
+spt_status spt_debug_qgemv(int32_t device, int32_t dtype, int32_t ggml_type, const void* blocks, size_t blocks_bytes,
+                           int32_t N, int32_t K, const float* act, int32_t R, const float* ln_w, const float* ln_b,
+                           const float* bias, const float* resid, int32_t mode, int32_t a_src, int32_t ksplit,
+                           float* out_plain, float* out_packed, float* top_plain, float* top_packed, float* unpacked,
+                           char* err, size_t errlen);
 
 /* ================================================================================================
  * ABI 6: Parakeet-V3 (NeMo FastConformer-TDT), the app's other local engine;

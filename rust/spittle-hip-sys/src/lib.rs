@@ -31,6 +31,18 @@ pub const SPT_ATTN_CROSS_VW: i32 = 1;
 pub const SPT_ATTN_CROSS_VW_PQ: i32 = 2;
 pub const SPT_ATTN_CROSS_VW_MERGE: i32 = 3;
 pub const SPT_ATTN_CROSS_VW_PQ_MERGE: i32 = 4;
+/// `spt_debug_qgemv`: the ggml types with a resident layout, the GEMV modes and A sources
+pub const SPT_GGML_Q4_1: i32 = 3;
+pub const SPT_GGML_Q5_0: i32 = 6;
+pub const SPT_GGML_Q5_1: i32 = 7;
+pub const SPT_GV_BIAS: i32 = 0;
+pub const SPT_GV_BIAS_GELU: i32 = 1;
+pub const SPT_GV_PARTIAL: i32 = 2;
+pub const SPT_GV_QKV_CACHE: i32 = 3;
+pub const SPT_GV_LOGITS: i32 = 4;
+pub const SPT_GV_BIAS_RESID: i32 = 5;
+pub const SPT_QGEMV_A_DIRECT: i32 = 0;
+pub const SPT_QGEMV_A_LN: i32 = 1;
 /// `spt_pk_act` of `spt_parakeet_debug_qgemm`
 pub const SPT_PK_ACT_NONE: i32 = 0;
 pub const SPT_PK_ACT_RELU: i32 = 1;
@@ -42,6 +54,8 @@ pub const SPT_IGNORE_EOT: u32 = 4;
 pub const SPT_SUPPRESS_NST: u32 = 8;
 
 pub const SPT_MODEL_WEIGHTS_EXTERNAL: u32 = 1;
+/// quantised decoder matrices of a ggml file stay resident in their blocks (SPT_HAS_QUANT_RESIDENT)
+pub const SPT_MODEL_QUANT_RESIDENT: u32 = 2;
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -396,6 +410,38 @@ extern "C" {
         share: i32,
         out: *mut f32,
         part: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_get_weight_residency(
+        ctx: *const spt_ctx,
+        resident_weights: *mut i64,
+        resident_bytes: *mut i64,
+        ggml_type: *mut i32,
+    ) -> spt_status;
+    // the decoder GEMV alone over one quantised matrix, expanded and packed (SPT_HAS_QUANT_RESIDENT)
+    pub fn spt_debug_qgemv(
+        device: i32,
+        dtype: i32,
+        ggml_type: i32,
+        blocks: *const c_void,
+        blocks_bytes: usize,
+        n: i32,
+        k: i32,
+        act: *const f32,
+        r: i32,
+        ln_w: *const f32,
+        ln_b: *const f32,
+        bias: *const f32,
+        resid: *const f32,
+        mode: i32,
+        a_src: i32,
+        ksplit: i32,
+        out_plain: *mut f32,
+        out_packed: *mut f32,
+        top_plain: *mut f32,
+        top_packed: *mut f32,
+        unpacked: *mut f32,
         err: *mut c_char,
         errlen: usize,
     ) -> spt_status;

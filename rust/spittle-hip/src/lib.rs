@@ -176,6 +176,34 @@ impl HipWhisperEngine {
         self.load_model_raw(model_path, model_params_f16(&params))
     }
 
+    /// Load option `SPT_MODEL_QUANT_RESIDENT`: the file's q4_1 / q5_0 / q5_1 decoder matrices and token
+    /// embedding stay quantised in HBM (the catalog's `large`, ggml-large-v3-q5_0.bin, and `medium`,
+    /// whisper-medium-q4_1.bin, are the files this serves; q5_K `breeze-asr` loads with nothing
+    /// resident).  Results are bit for bit those of `load_model_with_params` / `load_model_f16`; the
+    /// weight arena shrinks, the decode pass does not get faster.  `f16`: the fp16 engine, else bf16
+    /// (`params.bf16` is ignored: the f32 engine keeps no quantised matrices).
+    pub fn load_model_quant_resident(&mut self, model_path: &Path, params: HipModelParams, f16: bool) -> Result<(), Box<dyn Error>> {
+        let mut mp = model_params_f16(&params);
+        if !f16 {
+            mp.dtype = sys::SPT_DTYPE_BF16;
+        }
+        mp.flags |= sys::SPT_MODEL_QUANT_RESIDENT;
+        self.load_model_raw(model_path, mp)
+    }
+
+    /// What `load_model_quant_resident` kept: (weights held quantised, their bytes in the arena, their
+    /// ggml type or -1 for none / several).
+    pub fn weight_residency(&self) -> Result<(i64, i64, i32), Box<dyn Error>> {
+        self.need()?;
+        let (mut w, mut b, mut t) = (0i64, 0i64, -1i32);
+        // SAFETY: a live context and three valid out-pointers
+        let st = unsafe { sys::spt_get_weight_residency(self.ctx, &mut w, &mut b, &mut t) };
+        if st != sys::SPT_OK {
+            return Err(status_error("weight residency", st, self.last_error()));
+        }
+        Ok((w, b, t))
+    }
+
     /// Several utterances in one call (each <= 30 s window is a batch row).
     pub fn transcribe_batch(
         &mut self,

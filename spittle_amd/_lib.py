@@ -61,7 +61,13 @@ EXPORTS = [
     "spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather",
     # the attention kernels alone (test hooks, additive over ABI 14)
     "spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross",
+    # quantised decoder weights resident in HBM (SPT_HAS_QUANT_RESIDENT)
+    "spt_debug_qgemv", "spt_get_weight_residency",
 ]
+SPT_MODEL_QUANT_RESIDENT = 2
+SPT_GGML_Q4_1, SPT_GGML_Q5_0, SPT_GGML_Q5_1 = 3, 6, 7
+SPT_GV_BIAS, SPT_GV_BIAS_GELU, SPT_GV_PARTIAL, SPT_GV_QKV_CACHE, SPT_GV_LOGITS, SPT_GV_BIAS_RESID = range(6)
+SPT_QGEMV_A_DIRECT, SPT_QGEMV_A_LN = 0, 1
 SPT_ATTN_CROSS_8WAVE, SPT_ATTN_CROSS_VW, SPT_ATTN_CROSS_VW_PQ, SPT_ATTN_CROSS_VW_MERGE, SPT_ATTN_CROSS_VW_PQ_MERGE = range(5)
 SPT_SV_LANG_AUTO, SPT_SV_LANG_ZH, SPT_SV_LANG_EN, SPT_SV_LANG_YUE, SPT_SV_LANG_JA, SPT_SV_LANG_KO = range(6)
 SPT_PK_WEIGHTS_EMPTY = 1
@@ -424,6 +430,11 @@ def load():
                                        i32, fp, fp, C.c_char_p, C.c_size_t]
     for fn in ("spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross"):
         getattr(L, fn).restype = C.c_int
+    L.spt_debug_qgemv.argtypes = [i32, i32, i32, C.c_void_p, C.c_size_t, i32, i32, fp, i32, fp, fp, fp, fp, i32, i32,
+                                  i32, fp, fp, fp, fp, fp, C.c_char_p, C.c_size_t]
+    L.spt_debug_qgemv.restype = C.c_int
+    L.spt_get_weight_residency.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    L.spt_get_weight_residency.restype = C.c_int
     for fn in EXPORTS:
         if fn.startswith("spt_parakeet_") and fn not in ("spt_parakeet_default_model_params",
                                                           "spt_parakeet_default_infer_params", "spt_parakeet_destroy",

@@ -348,7 +348,7 @@ spt_status run_windows(spt_ctx* c, std::vector<Window>& win, const float* const*
 
 extern "C" {
 
-const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice)"; }
+const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice, qresident)"; }
 
 const char* spt_language_code(int32_t lang_id) { return spt::lang_code(lang_id); }
 
@@ -390,9 +390,13 @@ spt_status spt_ctx_create(const char* model_spec, const spt_model_params* params
         set_err(err, errlen, "bad dtype");
         return SPT_ERR_INVALID_ARG;
     }
-    if (mp.flags & ~SPT_MODEL_WEIGHTS_EXTERNAL) {
+    if (mp.flags & ~(SPT_MODEL_WEIGHTS_EXTERNAL | SPT_MODEL_QUANT_RESIDENT)) {
         set_err(err, errlen, "unknown spt_model_params.flags bits");
         return SPT_ERR_INVALID_ARG;
+    }
+    if ((mp.flags & SPT_MODEL_QUANT_RESIDENT) && mp.dtype == SPT_DTYPE_F32) {
+        set_err(err, errlen, "SPT_MODEL_QUANT_RESIDENT needs a bf16 or f16 engine (the f32 engine keeps no quantised matrices)");
+        return SPT_ERR_UNSUPPORTED;
     }
     spt::ModelDims dm;
     uint64_t seed = mp.seed;
@@ -430,7 +434,8 @@ spt_status spt_ctx_create(const char* model_spec, const spt_model_params* params
     if (!c) return SPT_ERR_OOM;
     try {
         c->eng.reset(new Engine(dm, mp.dtype == SPT_DTYPE_BF16 ? spt::DT_BF16 : mp.dtype == SPT_DTYPE_F16 ? spt::DT_F16 : spt::DT_F32, mp.device,
-                                mp.max_batch, seed, file.get(), (mp.flags & SPT_MODEL_WEIGHTS_EXTERNAL) != 0));
+                                mp.max_batch, seed, file.get(), (mp.flags & SPT_MODEL_WEIGHTS_EXTERNAL) != 0,
+                                (mp.flags & SPT_MODEL_QUANT_RESIDENT) != 0));
         if (file) c->vocab.reset(new spt::Vocab(file->vocab(), dm.n_vocab, spt::specials_for(dm.n_vocab)));
     } catch (const std::exception& e) {
         set_err(err, errlen, e.what());
@@ -644,6 +649,18 @@ spt_status spt_get_xq_stats(const spt_ctx* ctx, int32_t* fused_launches, int32_t
     const spt::CallStats& c = ctx->eng->call_stats();
     if (fused_launches) *fused_launches = c.xq_fused;
     if (fallbacks) *fallbacks = c.xq_fallbacks;
+    return SPT_OK;
+}
+
+spt_status spt_get_weight_residency(const spt_ctx* ctx, int64_t* resident_weights, int64_t* resident_bytes,
+                                    int32_t* ggml_type) {
+    if (!ctx) return SPT_ERR_INVALID_ARG;
+    int64_t w = 0, b = 0;
+    int t = -1;
+    ctx->eng->weight_residency(&w, &b, &t);
+    if (resident_weights) *resident_weights = w;
+    if (resident_bytes) *resident_bytes = b;
+    if (ggml_type) *ggml_type = t;
     return SPT_OK;
 }
 

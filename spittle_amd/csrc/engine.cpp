@@ -9,6 +9,7 @@
 // protocol of BASELINE.md.
 #include "engine.h"
 #include "ggml_file.h"
+#include "ggml_qpack.h"
 
 #include <cstdio>
 
@@ -86,8 +87,10 @@ struct Carver {
 void Engine::select() const { HIP_CHECK(hipSetDevice(dev_)); }
 
 Engine::Engine(const ModelDims& dm, int dtype, int device, int max_batch, uint64_t seed, const GgmlFile* src,
-               bool external_weights)
+               bool external_weights, bool quant_resident)
     : dm_(dm), dt_(dtype), dev_(device), max_batch_(max_batch), seed_(seed) {
+    if (quant_resident && dtype == DT_F32)
+        throw std::runtime_error("SPT_MODEL_QUANT_RESIDENT needs a bf16 or f16 engine");
     if (dm_.d % 128 || dm_.d / 64 != dm_.n_head) throw std::runtime_error("unsupported model width");
     if (max_batch_ < 1 || max_batch_ > 64) throw std::runtime_error("max_batch must be in 1..64");
     if (dt_ == DT_F32 && dm_.d > 1024)  // LayerNorm-prologue GEMVs stage <= 16 f32 super-steps
@@ -123,6 +126,10 @@ Engine::Engine(const ModelDims& dm, int dtype, int device, int max_batch, uint64
     try {
         gemv_prepare(dt_);
         gemm_prepare();  // > 64 KiB LDS attributes on this device, before any capture
+        enc_.resize(dm_.n_enc);
+        dec_.resize(dm_.n_dec);
+        if (quant_resident && src) plan_residency(*src);
+        if (res_weights_) gemv_q_prepare(dt_);
         alloc_weights();
         if (external_weights) {
             // filled later by import_weights; clear it so a premature use reads zeros, not garbage
@@ -223,12 +230,12 @@ void Engine::commit_weights() {
 
 void Engine::alloc_weights() {
     const int64_t d = dm_.d, dd = d * d, V = dm_.n_vocab, L = dm_.n_dec;
-    enc_.resize(dm_.n_enc);
-    dec_.resize(dm_.n_dec);
     for (int pass = 0; pass < 2; ++pass) {
         Carver c{pass ? warena_ : nullptr};
         auto W = [&](int64_t n) { return c.take(n * esz_); };
         auto F = [&](int64_t n) { return (float*)c.take(n * 4); };
+        // a [N][K] decoder matrix: in the engine dtype, or (q != 0) in its packed blocks
+        auto WQ = [&](int64_t N, int64_t K, int q) { return q ? c.take(qpack_bytes(q, N, K)) : W(N * K); };
         conv1_w_ = W(d * 3 * cp_); conv1_b_ = F(d);
         conv2_w_ = W(dd * 3); conv2_b_ = F(d);
         enc_pos_ = F((int64_t)dm_.n_audio_ctx * d);
@@ -238,11 +245,13 @@ void Engine::alloc_weights() {
             e.ln2_w = F(d); e.ln2_b = F(d); e.fc1_w = W(4 * dd); e.fc1_b = F(4 * d); e.fc2_w = W(4 * dd); e.fc2_b = F(d);
         }
         ckv_w_ = W(L * 2 * dd); ckv_b_ = F(L * 2 * d);
-        tok_emb_ = W(V * d); dec_pos_ = F((int64_t)dm_.n_text_ctx * d); lnf_w_ = F(d); lnf_b_ = F(d);
+        tok_emb_ = WQ(V, d, tok_q_); dec_pos_ = F((int64_t)dm_.n_text_ctx * d); lnf_w_ = F(d); lnf_b_ = F(d);
         for (auto& e : dec_) {
-            e.ln1_w = F(d); e.ln1_b = F(d); e.qkv_w = W(3 * dd); e.qkv_b = F(3 * d); e.so_w = W(dd); e.so_b = F(d);
-            e.ln2_w = F(d); e.ln2_b = F(d); e.cq_w = W(dd); e.cq_b = F(d); e.co_w = W(dd); e.co_b = F(d);
-            e.ln3_w = F(d); e.ln3_b = F(d); e.fc1_w = W(4 * dd); e.fc1_b = F(4 * d); e.fc2_w = W(4 * dd); e.fc2_b = F(d);
+            e.ln1_w = F(d); e.ln1_b = F(d); e.qkv_w = WQ(3 * d, d, e.qkv_q); e.qkv_b = F(3 * d);
+            e.so_w = WQ(d, d, e.so_q); e.so_b = F(d);
+            e.ln2_w = F(d); e.ln2_b = F(d); e.cq_w = WQ(d, d, e.cq_q); e.cq_b = F(d); e.co_w = WQ(d, d, e.co_q); e.co_b = F(d);
+            e.ln3_w = F(d); e.ln3_b = F(d); e.fc1_w = WQ(4 * d, d, e.fc1_q); e.fc1_b = F(4 * d);
+            e.fc2_w = WQ(d, 4 * d, e.fc2_q); e.fc2_b = F(d);
         }
         if (!pass) {
             wbytes_ = c.off;
@@ -374,6 +383,43 @@ bool ggml_dims(const GgmlFile& f, ModelDims* dm, std::string* err) {
 // projection into ckv_w_ rows [2l d, 2l d + 2d).  Conv kernels are re-laid [d][C][3] ->
 // [d][3][Cp] (Cp = padded mel channels) for the implicit-GEMM convolution.  Tensor ids match
 // generate_weights() so the checksum probes address both kinds of model alike.
+// SPT_MODEL_QUANT_RESIDENT: a decoder matrix (and the token embedding) whose tensors are all of one type
+// with a packed layout stays in its blocks; any other falls back to dequantisation at load.  The plan
+// is a function of the file's tensor types alone, so two contexts of the same file and flag lay out
+// the same arena.
+void Engine::plan_residency(const GgmlFile& f) {
+    const int64_t d = dm_.d;
+    int64_t n_types = 0;
+    auto type_of = [&](std::initializer_list<std::string> names, int64_t N, int64_t K) -> int {
+        int q = 0;
+        for (const std::string& nm : names) {
+            const GgmlTensor* t = f.find(nm);
+            QPackGeom g;
+            if (!t || !qpack_geom(t->type, &g) || (q && t->type != q)) return 0;
+            q = t->type;
+        }
+        res_weights_ += N * K;
+        res_bytes_ += qpack_bytes(q, N, K);
+        if (res_type_ != q) {
+            res_type_ = q;
+            ++n_types;
+        }
+        return q;
+    };
+    tok_q_ = type_of({"decoder.token_embedding.weight"}, dm_.n_vocab, d);
+    for (int l = 0; l < dm_.n_dec; ++l) {
+        DecL& e = dec_[l];
+        const std::string p = "decoder.blocks." + std::to_string(l) + ".";
+        e.qkv_q = type_of({p + "attn.query.weight", p + "attn.key.weight", p + "attn.value.weight"}, 3 * d, d);
+        e.so_q = type_of({p + "attn.out.weight"}, d, d);
+        e.cq_q = type_of({p + "cross_attn.query.weight"}, d, d);
+        e.co_q = type_of({p + "cross_attn.out.weight"}, d, d);
+        e.fc1_q = type_of({p + "mlp.0.weight"}, 4 * d, d);
+        e.fc2_q = type_of({p + "mlp.2.weight"}, d, 4 * d);
+    }
+    if (n_types != 1) res_type_ = -1;
+}
+
 void Engine::load_ggml(const GgmlFile& f) {
     const int64_t d = dm_.d, dd = d * d;
     std::vector<std::pair<const GgmlTensor*, std::string>> used;
@@ -404,6 +450,27 @@ void Engine::load_ggml(const GgmlFile& f) {
         auto putf = [&](const std::string& name, int64_t n, float* dst, int tid) { put(name, n, dst, DT_F32, tid); };
         auto putw = [&](const std::string& name, int64_t n, void* dst, int tid) { put(name, n, dst, dt_, tid); };
         auto at = [&](void* p, int64_t elems) { return (void*)((char*)p + elems * esz_); };
+        // rows [row0, row0 + N) of a decoder matrix of width K at `base`: packed on the host into the
+        // resident layout (q != 0), or dequantised on the device as every other matrix
+        std::vector<uint8_t> packed;
+        auto putm = [&](const std::string& name, int64_t N, int64_t K, void* base, int64_t row0, int q, int tid) {
+            if (!q) {
+                putw(name, N * K, at(base, row0 * K), tid);
+                return;
+            }
+            const GgmlTensor* t = need(name, N * K);
+            if (!pass) return;
+            if (t->type != q) throw std::runtime_error("tensor " + name + " is not of the planned resident type");
+            packed.resize((size_t)qpack_bytes(q, N, K));
+            if (!qpack_rows(q, t->data, t->nbytes, N, K, packed.data()))
+                throw std::runtime_error("tensor " + name + " is shorter than its blocks");
+            void* dst = (char*)base + qpack_bytes(q, row0, K);
+            HIP_CHECK(hipMemcpy(dst, packed.data(), packed.size(), hipMemcpyHostToDevice));
+            TRef r{dst, N * K, dt_};
+            r.q = q;
+            r.K = K;
+            tref_[tid] = r;
+        };
         auto conv = [&](const std::string& name, int C, int Cp, void* dst, int tid) {
             const GgmlTensor* t = need(name, d * C * 3);
             if (!pass) return;
@@ -455,7 +522,7 @@ void Engine::load_ggml(const GgmlFile& f) {
             putf(p + "mlp.2.bias", d, e.fc2_b, b + 14);
             if (pass) fill_f32(e.qkv_b + d, d, 0.0f, st_);
         }
-        putw("decoder.token_embedding.weight", (int64_t)dm_.n_vocab * d, tok_emb_, 10);
+        putm("decoder.token_embedding.weight", dm_.n_vocab, d, tok_emb_, 0, tok_q_, 10);
         putf("decoder.positional_embedding", (int64_t)dm_.n_text_ctx * d, dec_pos_, 11);
         putf("decoder.ln.weight", d, lnf_w_, 12);
         putf("decoder.ln.bias", d, lnf_b_, 13);
@@ -465,27 +532,27 @@ void Engine::load_ggml(const GgmlFile& f) {
             const std::string p = "decoder.blocks." + std::to_string(l) + ".";
             putf(p + "attn_ln.weight", d, e.ln1_w, b + 0);
             putf(p + "attn_ln.bias", d, e.ln1_b, b + 1);
-            putw(p + "attn.query.weight", dd, at(e.qkv_w, 0), b + 2);
+            putm(p + "attn.query.weight", d, d, e.qkv_w, 0, e.qkv_q, b + 2);
             putf(p + "attn.query.bias", d, e.qkv_b, b + 3);
-            putw(p + "attn.key.weight", dd, at(e.qkv_w, dd), b + 4);
-            putw(p + "attn.value.weight", dd, at(e.qkv_w, 2 * dd), b + 5);
+            putm(p + "attn.key.weight", d, d, e.qkv_w, d, e.qkv_q, b + 4);
+            putm(p + "attn.value.weight", d, d, e.qkv_w, 2 * d, e.qkv_q, b + 5);
             putf(p + "attn.value.bias", d, e.qkv_b + 2 * d, b + 6);
-            putw(p + "attn.out.weight", dd, e.so_w, b + 7);
+            putm(p + "attn.out.weight", d, d, e.so_w, 0, e.so_q, b + 7);
             putf(p + "attn.out.bias", d, e.so_b, b + 8);
             putf(p + "cross_attn_ln.weight", d, e.ln2_w, b + 9);
             putf(p + "cross_attn_ln.bias", d, e.ln2_b, b + 10);
-            putw(p + "cross_attn.query.weight", dd, e.cq_w, b + 11);
+            putm(p + "cross_attn.query.weight", d, d, e.cq_w, 0, e.cq_q, b + 11);
             putf(p + "cross_attn.query.bias", d, e.cq_b, b + 12);
             putw(p + "cross_attn.key.weight", dd, at(ckv_w_, (2 * l) * dd), b + 13);
             putw(p + "cross_attn.value.weight", dd, at(ckv_w_, (2 * l + 1) * dd), b + 14);
             putf(p + "cross_attn.value.bias", d, ckv_b_ + (2 * l + 1) * d, b + 15);
-            putw(p + "cross_attn.out.weight", dd, e.co_w, b + 16);
+            putm(p + "cross_attn.out.weight", d, d, e.co_w, 0, e.co_q, b + 16);
             putf(p + "cross_attn.out.bias", d, e.co_b, b + 17);
             putf(p + "mlp_ln.weight", d, e.ln3_w, b + 18);
             putf(p + "mlp_ln.bias", d, e.ln3_b, b + 19);
-            putw(p + "mlp.0.weight", 4 * dd, e.fc1_w, b + 20);
+            putm(p + "mlp.0.weight", 4 * d, d, e.fc1_w, 0, e.fc1_q, b + 20);
             putf(p + "mlp.0.bias", 4 * d, e.fc1_b, b + 21);
-            putw(p + "mlp.2.weight", 4 * dd, e.fc2_w, b + 22);
+            putm(p + "mlp.2.weight", d, 4 * d, e.fc2_w, 0, e.fc2_q, b + 22);
             putf(p + "mlp.2.bias", d, e.fc2_b, b + 23);
             if (pass) {
                 fill_f32(e.qkv_b + d, d, 0.0f, st_);
@@ -986,7 +1053,7 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
         {
             GemvArgs a{};
             ln_input(a); a.lda = d; a.ln_w = e.ln1_w; a.ln_b = e.ln1_b; a.R = R;
-            a.W = e.qkv_w; a.N = 3 * d; a.K = d; a.bias = e.qkv_b; a.C = g.dq; a.ldc = d;
+            a.W = e.qkv_w; a.wq = e.qkv_q; a.N = 3 * d; a.K = d; a.bias = e.qkv_b; a.C = g.dq; a.ldc = d;
             a.cache = skv_l; a.cache_B = B; a.cache_H = H; a.cache_ctx = ctx; a.Tq = Tq; a.st = g.ds;
             gemv(dt_, GV_QKV_CACHE, A_LN, a, st);
             consumed();
@@ -997,13 +1064,13 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
         // self-attention output projection, residual add in place: the cross-Q LayerNorm
         // prologue then reads x alone (r1 exp24: +0.4 % RTFx over a 2-way K split into slabs)
         GemvArgs a{};
-        a.A = g.dao; a.lda = d; a.R = R; a.W = e.so_w; a.N = d; a.K = d; a.bias = e.so_b;
+        a.A = g.dao; a.lda = d; a.R = R; a.W = e.so_w; a.wq = e.so_q; a.N = d; a.K = d; a.bias = e.so_b;
         a.C = xc; a.ldc = d;
         gemv(dt_, GV_BIAS_RESID, A_DIRECT, a, st);
         // LN2 + cross-Q projection
         a = GemvArgs{};
         ln_input(a); a.lda = d; a.ln_w = e.ln2_w; a.ln_b = e.ln2_b; a.R = R;
-        a.W = e.cq_w; a.N = d; a.K = d; a.bias = e.cq_b; a.C = g.dq; a.ldc = d;
+        a.W = e.cq_w; a.wq = e.cq_q; a.N = d; a.K = d; a.bias = e.cq_b; a.C = g.dq; a.ldc = d;
         if (fuse) {
             if (np != 0) throw std::runtime_error("fused cross-Q launch: pending slabs before LN2");
             XqFuseArgs x{};
@@ -1027,20 +1094,20 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
         pmark(0, l, 1);
         // cross output projection (merging the key chunks in its prologue), residual add in place
         a = GemvArgs{};
-        a.A = g.dao; a.lda = d; a.R = R; a.W = e.co_w; a.N = d; a.K = d; a.bias = e.co_b; a.C = xc; a.ldc = d;
+        a.A = g.dao; a.lda = d; a.R = R; a.W = e.co_w; a.wq = e.co_q; a.N = d; a.K = d; a.bias = e.co_b; a.C = xc; a.ldc = d;
         if (xs > 1) { a.apart = g.xpart; a.a_splits = xs; a.a_heads = H; }
         gemv(dt_, GV_BIAS_RESID, xs > 1 ? A_ATTN : A_DIRECT, a, st);
         // LN3 + fc1 + GELU
         a = GemvArgs{};
         ln_input(a); a.lda = d; a.ln_w = e.ln3_w; a.ln_b = e.ln3_b; a.R = R;
-        a.W = e.fc1_w; a.N = 4 * d; a.K = d; a.bias = e.fc1_b; a.C = g.dff; a.ldc = 4 * d;
+        a.W = e.fc1_w; a.wq = e.fc1_q; a.N = 4 * d; a.K = d; a.bias = e.fc1_b; a.C = g.dff; a.ldc = 4 * d;
         pmark(3, l, 0);
         gemv(dt_, GV_BIAS_GELU, A_LN, a, st);
         pmark(3, l, 1);
         consumed();
         // fc2 -> pending slabs
         a = GemvArgs{};
-        a.A = g.dff; a.lda = 4 * d; a.R = R; a.W = e.fc2_w; a.N = d; a.K = 4 * d; a.bias = e.fc2_b;
+        a.A = g.dff; a.lda = 4 * d; a.R = R; a.W = e.fc2_w; a.wq = e.fc2_q; a.N = d; a.K = 4 * d; a.bias = e.fc2_b;
         partial(a, fc2_split_);
         gemv(dt_, GV_PARTIAL, A_DIRECT, a, st);
     }
@@ -1069,7 +1136,7 @@ void Engine::enqueue_head(DecGroup& g, int Tq, const DecodeRequest& rq, int out_
     // combined rows are not needed
     ln_source(a, xc, g.pend, fc2_split_, (int64_t)R * d);
     a.lda = Tq * d; a.a_row0 = (Tq - 1) * d; a.ln_w = lnf_w_; a.ln_b = lnf_b_; a.R = B;
-    a.W = tok_emb_; a.N = dm_.n_vocab; a.K = d; a.C = g.logits; a.ldc = dm_.n_vocab; a.st = g.ds;
+    a.W = tok_emb_; a.wq = tok_q_; a.N = dm_.n_vocab; a.K = d; a.C = g.logits; a.ldc = dm_.n_vocab; a.st = g.ds;
     a.suppress = sup;
     a.blank0 = blank ? sp.eot : -1;
     a.blank1 = blank ? 220 : -1;
@@ -1095,7 +1162,7 @@ void Engine::enqueue_head(DecGroup& g, int Tq, const DecodeRequest& rq, int out_
         t.forced = rq.n_forced > 0 ? g.forced : nullptr; t.forced_len = rq.n_forced;
         t.next_tok = g.tok_in; t.out_tok = g.out_tok; t.out_plog = g.out_t1; t.out_tid = g.out_t2; t.out_cap = out_cap;
         t.done = g.done;
-        t.emb = tok_emb_; t.pos = dec_pos_; t.d = d; t.ctx = ctx; t.Tq = Tq; t.x = g.dx;
+        t.emb = tok_emb_; t.emb_q = tok_q_; t.pos = dec_pos_; t.d = d; t.ctx = ctx; t.Tq = Tq; t.x = g.dx;
         t.ds = g.ds; t.arrive = g.arrive; t.stat = g.ts_stat;
         dec_ts_stats(t, B, st);
         dec_finalize_ts(dt_, t, B, st);
@@ -1107,7 +1174,7 @@ void Engine::enqueue_head(DecGroup& g, int Tq, const DecodeRequest& rq, int out_
     f.forced = rq.n_forced > 0 ? g.forced : nullptr; f.forced_len = rq.n_forced;
     f.next_tok = g.tok_in; f.out_tok = g.out_tok; f.out_top1 = g.out_t1; f.out_top2 = g.out_t2; f.out_cap = out_cap;
     f.done = g.done;
-    f.emb = tok_emb_; f.pos = dec_pos_; f.d = d; f.ctx = ctx; f.Tq = Tq; f.x = g.dx;
+    f.emb = tok_emb_; f.emb_q = tok_q_; f.pos = dec_pos_; f.d = d; f.ctx = ctx; f.Tq = Tq; f.x = g.dx;
     f.ds = g.ds; f.arrive = g.arrive;
     dec_finalize(dt_, f, B, st);
 }
@@ -1269,7 +1336,7 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
         for (DecGroup* g : act) {
             reset_outputs(*g);
             upload_tokens(*g, [&](int, int) { return sp.sot; }, 1);
-            dec_embed(dt_, g->tok_in, g->B, 1, dm_.d, tok_emb_, dec_pos_, g->ds, g->dx, g->st);
+            dec_embed(dt_, g->tok_in, g->B, 1, dm_.d, tok_emb_, tok_q_, dec_pos_, g->ds, g->dx, g->st);
             float* x = enqueue_layers(*g, E, 1);
             enqueue_head(*g, 1, dq, out_cap, x, suppress_lang_, false);
         }
@@ -1299,7 +1366,7 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
         for (int c0 = 0; c0 < P; c0 += cmax) {
             const int n = std::min(cmax, P - c0);
             upload_tokens(g, [&](int b, int t) { return rows ? rq.row_prefix[b][c0 + t] : rq.prefix[c0 + t]; }, n);
-            dec_embed(dt_, g.tok_in, g.B * n, n, dm_.d, tok_emb_, dec_pos_, g.ds, g.dx, g.st);
+            dec_embed(dt_, g.tok_in, g.B * n, n, dm_.d, tok_emb_, tok_q_, dec_pos_, g.ds, g.dx, g.st);
             enqueue_layers(g, E, n);
             dec_advance(g.ds, n, g.st);
         }
@@ -1307,12 +1374,12 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
         for (int c0 = 0; c0 < Tq - Tq_head; c0 += cmax) {  // only when Bg * Tq > max_rows_
             const int n = std::min(cmax, Tq - Tq_head - c0);
             upload_tokens(g, [&](int b, int t) { return prompt_tok(b, c0 + t); }, n);
-            dec_embed(dt_, g.tok_in, g.B * n, n, dm_.d, tok_emb_, dec_pos_, g.ds, g.dx, g.st);
+            dec_embed(dt_, g.tok_in, g.B * n, n, dm_.d, tok_emb_, tok_q_, dec_pos_, g.ds, g.dx, g.st);
             enqueue_layers(g, E, n);
             dec_advance(g.ds, n, g.st);
         }
         upload_tokens(g, [&](int b, int t) { return prompt_tok(b, Tq - Tq_head + t); }, Tq_head);
-        dec_embed(dt_, g.tok_in, g.B * Tq_head, Tq_head, dm_.d, tok_emb_, dec_pos_, g.ds, g.dx, g.st);
+        dec_embed(dt_, g.tok_in, g.B * Tq_head, Tq_head, dm_.d, tok_emb_, tok_q_, dec_pos_, g.ds, g.dx, g.st);
         if (rq.beam_k > 0) {  // the first step's state: no tokens yet
             beam_host_.assign((size_t)g.B * 4 + 1, 0);
             for (int b = 0; b < g.B; ++b) beam_host_[b * 4 + 3] = 3000;
@@ -1579,7 +1646,7 @@ void Engine::beam_next(const int* src, const int* tokens, const int* rowstate, i
     void* const kv_to = side ? own : kvtmp_;
     auto beam_pass = [&] {
         dec_kv_gather(dt_, kv_from, kv_to, g.beam_src, dm_.n_dec, B, dm_.n_head, dm_.n_text_ctx, g.ds, g.st);
-        dec_embed(dt_, g.tok_in, B, 1, dm_.d, tok_emb_, dec_pos_, g.ds, g.dx, g.st);
+        dec_embed(dt_, g.tok_in, B, 1, dm_.d, tok_emb_, tok_q_, dec_pos_, g.ds, g.dx, g.st);
         struct SkvSide {  // the layers append to / read kv_to; the group's pointer is restored on unwind
             DecGroup& g;
             void* own;
@@ -1667,7 +1734,8 @@ bool Engine::debug_weight_checksum(int tid, double* out2) {
     auto it = tref_.find(tid);
     if (it == tref_.end()) return false;
     HIP_CHECK(hipMemsetAsync(scratch_, 0, 16, st_));
-    tensor_checksum(it->second.dt, it->second.p, it->second.n, scratch_, st_);
+    if (it->second.q) tensor_checksum_q(it->second.dt, it->second.q, it->second.p, it->second.n, it->second.K, scratch_, st_);
+    else tensor_checksum(it->second.dt, it->second.p, it->second.n, scratch_, st_);
     HIP_CHECK(hipMemcpyAsync(out2, scratch_, 16, hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
     return true;
@@ -1712,7 +1780,7 @@ double Engine::probe(int kind, int iters, double* work, int* is_flops) {
                 GemvArgs a{};
                 a.A = g.dx; a.lda = d; a.ln_w = lnf_w_; a.ln_b = lnf_b_; a.R = Bg;
                 for (int p = 0; p < kMaxPend; ++p) a.pend[p] = zero_;
-                a.W = tok_emb_; a.N = V; a.K = d; a.C = g.logits; a.ldc = V; a.st = g.ds;
+                a.W = tok_emb_; a.wq = tok_q_; a.N = V; a.K = d; a.C = g.logits; a.ldc = V; a.st = g.ds;
                 a.suppress = suppress_; a.blank0 = a.blank1 = -1; a.part = g.part; a.n_tiles = (V + 15) / 16;
                 gemv(dt_, GV_LOGITS, A_LN, a, st_);
             };
@@ -1725,7 +1793,7 @@ double Engine::probe(int kind, int iters, double* work, int* is_flops) {
                 for (int l = 0; l < nl; ++l) {
                     a.A = g.dx; a.lda = d; a.ln_w = dec_[l].ln3_w; a.ln_b = dec_[l].ln3_b; a.R = Bg;
                     for (int p = 0; p < kMaxPend; ++p) a.pend[p] = zero_;
-                    a.W = dec_[l].fc1_w; a.N = 4 * d; a.K = d; a.bias = dec_[l].fc1_b; a.C = g.dff; a.ldc = 4 * d;
+                    a.W = dec_[l].fc1_w; a.wq = dec_[l].fc1_q; a.N = 4 * d; a.K = d; a.bias = dec_[l].fc1_b; a.C = g.dff; a.ldc = 4 * d;
                     gemv(dt_, GV_BIAS_GELU, A_LN, a, st_);
                 }
             };
@@ -1791,7 +1859,7 @@ double Engine::probe(int kind, int iters, double* work, int* is_flops) {
                 GemvArgs a{};
                 ln_source(a, x, g.pend, fc2_split_, (int64_t)Bg * d);
                 a.lda = d; a.ln_w = lnf_w_; a.ln_b = lnf_b_; a.R = Bg;
-                a.W = tok_emb_; a.N = V; a.K = d; a.C = g.logits; a.ldc = V; a.st = g.ds;
+                a.W = tok_emb_; a.wq = tok_q_; a.N = V; a.K = d; a.C = g.logits; a.ldc = V; a.st = g.ds;
                 a.suppress = suppress_; a.blank0 = a.blank1 = -1; a.part = g.part; a.n_tiles = (V + 15) / 16;
                 HIP_CHECK(hipEventRecord(probe_ev_[0], g.st));
                 gemv(dt_, GV_LOGITS, A_LN, a, g.st);

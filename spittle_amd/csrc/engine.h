@@ -78,8 +78,10 @@ public:
     // (dm from ggml_dims(*src)); the file is read during construction only
     // external_weights: allocate the weight arena but leave it unfilled; import_weights() (e.g.
     // the bytes of rank 0's arena after an RCCL broadcast) makes the engine usable
+    // quant_resident (SPT_MODEL_QUANT_RESIDENT; bf16 / f16 engines, ggml files): the decoder's matrices and the
+    // token embedding whose file type has a packed layout (ggml_qpack.h) stay quantised in the arena
     Engine(const ModelDims& dm, int dtype, int device, int max_batch, uint64_t seed, const GgmlFile* src = nullptr,
-           bool external_weights = false);
+           bool external_weights = false, bool quant_resident = false);
     ~Engine();
     Engine(const Engine&) = delete;
     Engine& operator=(const Engine&) = delete;
@@ -89,6 +91,10 @@ public:
     int max_batch() const { return max_batch_; }
     int max_rows() const { return max_rows_; }  // decoder rows one pass carries (beam search: one group)
     int64_t weight_bytes() const { return wbytes_; }
+    // weights held quantised, their bytes in the arena, and their ggml type (-1: none, or several types)
+    void weight_residency(int64_t* weights, int64_t* bytes, int* type) const {
+        *weights = res_weights_; *bytes = res_bytes_; *type = res_type_;
+    }
     bool weights_ready() const { return weights_ready_; }
     // D2D copies of the whole weight arena (device pointers on this engine's device, or any
     // peer-accessible one); the arena layout is a pure function of (dims, dtype, n_mels padding),
@@ -273,12 +279,18 @@ private:
                   void* fc1_w; float* fc1_b; void* fc2_w; float* fc2_b; };
     struct DecL { float *ln1_w, *ln1_b; void* qkv_w; float* qkv_b; void* so_w; float* so_b; float *ln2_w, *ln2_b;
                   void* cq_w; float* cq_b; void* co_w; float* co_b; float *ln3_w, *ln3_b; void* fc1_w; float* fc1_b;
-                  void* fc2_w; float* fc2_b; };
+                  void* fc2_w; float* fc2_b;
+                  // ggml type of each matrix kept in its packed blocks (0: stored in the engine dtype)
+                  int qkv_q = 0, so_q = 0, cq_q = 0, co_q = 0, fc1_q = 0, fc2_q = 0; };
     void *conv1_w_, *conv2_w_, *ckv_w_, *tok_emb_;
+    int tok_q_ = 0;                                   // the token embedding's, likewise
+    int64_t res_weights_ = 0, res_bytes_ = 0;
+    int res_type_ = -1;
+    void plan_residency(const GgmlFile& f);           // before alloc_weights: which matrices stay packed
     float *conv1_b_, *conv2_b_, *enc_pos_, *lnp_w_, *lnp_b_, *ckv_b_, *dec_pos_, *lnf_w_, *lnf_b_;
     std::vector<EncL> enc_;
     std::vector<DecL> dec_;
-    struct TRef { void* p; int64_t n; int dt; };
+    struct TRef { void* p; int64_t n; int dt; int q = 0; int64_t K = 0; };  // q != 0: rows of a packed matrix of width K
     std::map<int, TRef> tref_;
     // (batch size, window groups) -> captured encoder (enqueue_encoder), and the keys whose first,
     // eager encoder call ran

@@ -73,6 +73,18 @@ __host__ __device__ inline void gq_scale_min_k4(int j, const uint8_t* q, int* sc
     }
 }
 
+// One element of a 4- or 5-bit 32-element block type (q4_0 / q4_1 / q5_0 / q5_1): code x (the nibble
+// with the fifth bit or-ed in), the type's offset, scale d and, for the _1 types, minimum m.  The one
+// spelling of this arithmetic: ggml_dequant_block below and the decoder GEMV's in-register
+// dequantisation of a resident matrix (dec_gemv.h) both call it, each product and sum rounded once.
+// (has_m is a select, not an add of zero: -0 + 0 would lose the sign of a zero product.)
+__host__ __device__ inline float gq_dequant_elem(int x, int off, float d, bool has_m, float m) {
+#pragma clang fp contract(off)
+    float v = (float)(x - off) * d;
+    if (has_m) v = v + m;
+    return v;
+}
+
 // dequantise one block (blck elements) of a quantised type: out(i, value) for i in [0, blck)
 template <typename Out>
 __host__ __device__ inline void ggml_dequant_block(int type, const uint8_t* p, Out out) {
@@ -102,13 +114,8 @@ __host__ __device__ inline void ggml_dequant_block(int type, const uint8_t* p, O
                     x0 |= ((qh >> j) << 4) & 0x10;
                     x1 |= (qh >> (j + 12)) & 0x10;
                 }
-                float v0 = (float)(x0 - off) * d, v1 = (float)(x1 - off) * d;
-                if (has_m) {
-                    v0 = v0 + m;
-                    v1 = v1 + m;
-                }
-                out(j, v0);
-                out(j + 16, v1);
+                out(j, gq_dequant_elem(x0, off, d, has_m, m));
+                out(j + 16, gq_dequant_elem(x1, off, d, has_m, m));
             }
             return;
         }

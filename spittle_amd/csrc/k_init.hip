@@ -8,6 +8,7 @@
 // are rounded to bf16 with round-to-nearest-even, exactly as the oracle does.
 #include "common.h"
 #include "kernels.h"
+#include "ggml_qpack.h"
 #include "ggml_quant.h"
 
 #include <type_traits>
@@ -64,6 +65,35 @@ __global__ void checksum_kernel(const T* src, int64_t n, double* out) {
     double a = 0, b = 0;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const double v = (double)to_f<T>(src[i]);
+        a += fabs(v);
+        b += v;
+    }
+    sa[threadIdx.x] = a;
+    sb[threadIdx.x] = b;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            sa[threadIdx.x] += sa[threadIdx.x + s];
+            sb[threadIdx.x] += sb[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        atomicAdd(&out[0], sa[0]);
+        atomicAdd(&out[1], sb[0]);
+    }
+}
+
+// checksum_kernel over a packed resident matrix: element i is row i / K, column i % K, dequantised and
+// rounded to T (the value the loader's dequantisation would have stored), summed in the same partition
+template <typename T>
+__global__ void checksum_q_kernel(int qtype, const uint8_t* src, int64_t n, int64_t K, double* out) {
+    __shared__ double sa[256], sb[256];
+    QPackGeom g;
+    qpack_geom(qtype, &g);
+    double a = 0, b = 0;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = (double)to_f<T>(from_f<T>(qpack_at(g, src, K, i / K, i % K)));
         a += fabs(v);
         b += v;
     }
@@ -204,6 +234,19 @@ void tensor_checksum(int dtype, const void* src, int64_t n, double* out2, hipStr
         hipLaunchKernelGGL(checksum_kernel<f16>, dim3(g), dim3(256), 0, st, (const f16*)src, n, out2);
     else
         hipLaunchKernelGGL(checksum_kernel<float>, dim3(g), dim3(256), 0, st, (const float*)src, n, out2);
+}
+
+void tensor_checksum_q(int dtype, int qtype, const void* packed, int64_t n, int64_t K, double* out2, hipStream_t st) {
+    QPackGeom qg;
+    if (!qpack_geom(qtype, &qg) || K <= 0 || K % QPACK_KS || n % K)
+        throw std::runtime_error("tensor_checksum_q: not whole rows of a packed matrix");
+    int g = grid_for(n);
+    if (g > 1024) g = 1024;
+    if (dtype == DT_BF16)
+        hipLaunchKernelGGL(checksum_q_kernel<bf16>, dim3(g), dim3(256), 0, st, qtype, (const uint8_t*)packed, n, K, out2);
+    else if (dtype == DT_F16)
+        hipLaunchKernelGGL(checksum_q_kernel<f16>, dim3(g), dim3(256), 0, st, qtype, (const uint8_t*)packed, n, K, out2);
+    else throw std::runtime_error("tensor_checksum_q: a packed matrix needs a bf16 or f16 engine");
 }
 
 }  // namespace spt

@@ -24,6 +24,7 @@
 // The chosen (or forced) token is embedded for the next pass and the step advanced exactly
 // as dec_finalize does.
 #include "common.h"
+#include "ggml_qpack.h"
 #include "kernels.h"
 
 namespace spt {
@@ -180,7 +181,8 @@ __global__ __launch_bounds__(TS_T) void ts_stats_kernel(TsArgs a) {
     }
 }
 
-template <typename T>
+// QE: the token embedding is resident in its packed ggml blocks (a.emb_q; emb_row_read, ggml_qpack.h)
+template <typename T, bool QE = false>
 __global__ __launch_bounds__(TW) void finalize_ts_kernel(TsArgs a) {
     __shared__ float s_scan[TW];
     __shared__ int s_pick, s_tok;
@@ -339,9 +341,9 @@ __global__ __launch_bounds__(TW) void finalize_ts_kernel(TsArgs a) {
     const int pos0 = a.ds->pos0;
     const unsigned epoch = a.ds->epoch;
     const int pn = min(pos0 + a.Tq, a.ctx - 1);
-    const T* e = (const T*)a.emb + (size_t)tok * a.d;
     const float* pp = a.pos + (size_t)pn * a.d;
-    for (int i = tid; i < a.d; i += TW) a.x[(size_t)b * a.d + i] = to_f<T>(e[i]) + pp[i];
+    for (int i = tid; i < a.d; i += TW)
+        a.x[(size_t)b * a.d + i] = emb_row_read<T, QE>(a.emb, a.emb_q, a.d, tok, i) + pp[i];
     if (tid == 0) {
         // relaxed: every block's reads of the step state were consumed before it arrives, and the next
         // kernel sees the last arriver's plain stores across the launch boundary (an acq_rel RMW cost
@@ -690,6 +692,12 @@ void dec_ts_stats(const TsArgs& a, int B, hipStream_t st) {
 void dec_finalize_ts(int dtype, const TsArgs& a, int B, hipStream_t st) {
     if (!a.stat) throw std::runtime_error("finalize_ts: no chunk statistics (dec_ts_stats)");
     if (a.n_vocab < 1 || a.n_vocab > VJ * TW) throw std::runtime_error("finalize_ts: vocabulary above 53248 tokens");
+    if (a.emb_q) {  // a packed resident token embedding (16-bit engines)
+        if (dtype == DT_BF16) hipLaunchKernelGGL((finalize_ts_kernel<bf16, true>), dim3(B), dim3(TW), 0, st, a);
+        else if (dtype == DT_F16) hipLaunchKernelGGL((finalize_ts_kernel<f16, true>), dim3(B), dim3(TW), 0, st, a);
+        else throw std::runtime_error("dec_finalize_ts: a packed embedding needs a bf16 or f16 engine");
+        return;
+    }
     if (dtype == DT_BF16) hipLaunchKernelGGL(finalize_ts_kernel<bf16>, dim3(B), dim3(TW), 0, st, a);
     else if (dtype == DT_F16) hipLaunchKernelGGL(finalize_ts_kernel<f16>, dim3(B), dim3(TW), 0, st, a);
     else hipLaunchKernelGGL(finalize_ts_kernel<float>, dim3(B), dim3(TW), 0, st, a);

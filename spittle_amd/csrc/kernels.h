@@ -75,6 +75,9 @@ void dec_cross_attn_ni8(const void* q, const void* kv, int B, int B_layout, int 
 void stream_read(const void* p, int64_t bytes, unsigned* sink, int grid, int tpb, hipStream_t st);  // ubench probe
 // weight checksum helper for tests: sum of |w| and sum of w (f64) of a device tensor
 void tensor_checksum(int dtype, const void* src, int64_t n, double* out2_dev, hipStream_t st);
+// the same sums over n elements (whole rows of width K) of a packed resident matrix of ggml type qtype,
+// each element dequantised and rounded to dtype as the loader would have stored it
+void tensor_checksum_q(int dtype, int qtype, const void* packed, int64_t n, int64_t K, double* out2_dev, hipStream_t st);
 
 // ------------------------------------------------------------------ mel (k_mel.hip)
 struct MelTables {
@@ -144,6 +147,8 @@ struct GemvArgs {
     float* x_out;                         // A_LN: combined rows written here by workgroup (0, 0) (or nullptr)
     const float* apart; int a_splits, a_heads;  // A_ATTN: cross-attention chunk partials [R][H][S][66] (S = 2..4, 8)
     int R;                                // rows (<= 64)
+    int wq;                               // 0: W holds the engine dtype; else the ggml type (GQ_Q4_1 / Q5_0 / Q5_1)
+                                          // of a matrix resident in its packed blocks (ggml_qpack.h; 16-bit dtypes)
     const void* W; int N, K;              // W [N][K]
     const float* bias;
     void* C; int ldc;                     // output rows (GV_BIAS*, GV_LOGITS, GV_PARTIAL; GV_BIAS_RESID: f32 C += ...)
@@ -163,12 +168,18 @@ constexpr int kMaxPend = 4;
 void gemv(int dtype, int mode, int asrc, const GemvArgs& a, hipStream_t st);
 // one-time per-process kernel attributes (call before any stream capture)
 void gemv_prepare(int dtype);
+// k_dec_q.hip: the same kernels with the weights fetched from a packed quantised matrix (a.wq != 0).
+// gemv() checks its arguments and dispatches here (code: the kernel-side A source); gemv_q_prepare is
+// gemv_prepare for these kernels, needed only by a context that keeps matrices resident (bf16 / f16)
+void gemv_q(int dtype, int mode, int code, const GemvArgs& a, hipStream_t st);
+void gemv_q_prepare(int dtype);
 // rows a LayerNorm / attention-merge GEMV can stage for K columns (its LDS image budget): the
 // decoder's rows per pass (large-v3 bf16: 38; f32 small: 31; <= 64)
 int gemv_max_image_rows(int dtype, int K);
 
 // x[b*Tq + t] = tok_emb[tok[b*Tq+t]] + pos_emb[pos0 + t]
-void dec_embed(int dtype, const int* tok, int R, int Tq, int d, const void* tok_emb,
+// tok_q: 0, or the ggml type of a token embedding resident in its packed blocks (ggml_qpack.h)
+void dec_embed(int dtype, const int* tok, int R, int Tq, int d, const void* tok_emb, int tok_q,
                const float* pos_emb, const DecState* ds, float* x, hipStream_t st);
 // self attention over the cache: q [R][d] (row b*Tq + t at position pos0 + t), keys 0..pos0+t
 void dec_self_attn(int dtype, const void* q, const void* cache, int B, int H, int ctx, int Tq,
@@ -227,6 +238,7 @@ struct FinalizeArgs {
     const void* emb; const float* pos; int d, ctx, Tq;  // next-pass embedding -> x rows 0..B-1
     float* x;
     DecState* ds; unsigned* arrive;       // step state, last-arriver counter
+    int emb_q;                            // 0, or the ggml type of a packed resident embedding
 };
 // argmax reduce + record + next-token embed + step advance (replaces embed/argmax/advance)
 void dec_finalize(int dtype, const FinalizeArgs& a, int B, hipStream_t st);
@@ -259,6 +271,7 @@ struct TsArgs {
     float* x;
     DecState* ds; unsigned* arrive;
     float* stat;                         // [B][TS_CHUNKS][6] per-chunk maxima and sums (dec_ts_stats)
+    int emb_q;                           // 0, or the ggml type of a packed resident embedding
 };
 constexpr int TS_CHUNKS = 16;  // vocabulary chunks per row in dec_ts_stats
 // whisper_process_logits' maxima and exp sums of each row, over TS_CHUNKS workgroups per row

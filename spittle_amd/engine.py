@@ -43,6 +43,10 @@ class WhisperModelParams:
     # allocate the weight arena but leave it empty: import_weights() fills it (multi-GPU load,
     # rank 0's arena broadcast over RCCL; spittle_amd.dist.broadcast_weights)
     external_weights: bool = False
+    # SPT_MODEL_QUANT_RESIDENT: a ggml file's q4_1 / q5_0 / q5_1 decoder matrices and token embedding stay
+    # quantised in HBM and are dequantised in the decoder GEMVs (bf16 / f16 engines; results bit for bit
+    # those without it).  Opt-in: it shrinks the weight arena; the decode pass is not faster
+    quant_resident: bool = False
 
 
 @dataclass
@@ -174,7 +178,8 @@ class WhisperEngine:
         mp.device = int(self.params.device)
         mp.max_batch = int(self.params.max_batch)
         mp.seed = int(self.params.seed)
-        mp.flags = L.SPT_MODEL_WEIGHTS_EXTERNAL if self.params.external_weights else 0
+        mp.flags = (L.SPT_MODEL_WEIGHTS_EXTERNAL if self.params.external_weights else 0) | \
+                   (L.SPT_MODEL_QUANT_RESIDENT if self.params.quant_resident else 0)
         ctx = C.c_void_p()
         err = C.create_string_buffer(1024)
         st = self._lib.spt_ctx_create(str(model_path).encode(), C.byref(mp), C.byref(ctx), err, 1024)
@@ -325,6 +330,13 @@ class WhisperEngine:
         """whisper_token_to_str: the token's bytes (None for synthetic models / bad ids)."""
         self._need()
         return self._lib.spt_token_to_str(self._ctx, int(token))
+
+    def weight_residency(self) -> dict:
+        """What quant_resident kept: {"resident_weights", "resident_bytes" (in the arena, padding
+        included), "ggml_type" (-1: none, or several types)}."""
+        w, b, t = C.c_int64(), C.c_int64(), C.c_int32()
+        self._check(self._lib.spt_get_weight_residency(self._ctx, C.byref(w), C.byref(b), C.byref(t)))
+        return {"resident_weights": w.value, "resident_bytes": b.value, "ggml_type": t.value}
 
     def weight_checksum(self, tensor_id: int):
         self._need()
