@@ -376,6 +376,20 @@ spt_status spt_debug_attn_cross(int32_t device, int32_t dtype, int32_t mode, con
                                 const float* v, float pad_value, int32_t B, int32_t B_layout, int32_t b0, int32_t H,
                                 int32_t T_enc, int32_t Tq, int32_t splits, const int32_t* kvrow, int32_t share,
                                 float* out, float* part, char* err, size_t errlen);
+/* The fused cross-Q + cross-attention launch alone (dec_xq_fused; additive over
+ * ABI 14): x [B][1280] are the f32 residual rows, ln_w / ln_b [1280] the LayerNorm, wq [1280][1280] and
+ * bias [1280] the cross-Q projection, k, v [B][20][T_enc][64] and pad_value as spt_debug_attn_cross takes
+ * them (row b attends to window b).  wq, k and v are rounded to dtype on the host.  The call builds the
+ * step state, the granule buffer and the error word, runs the launch once and returns the projected
+ * q [B][1280] and the attention out [B][1280] as f32.  lds: key blocks per attention wave staged in LDS
+ * (0..2); touch: key blocks per wave touched before q arrives (0 or 2); neither changes a result bit.
+ * SPT_ERR_INVALID_ARG before any launch: dtype f32, H != 20, B outside 1..16, T_enc outside 256..1536,
+ * null buffers, lds / touch outside their values, or 80 + B * H above the device's compute units.  A
+ * consumer's wait for q that ran out is returned as SPT_ERR_DEVICE, never retried. */
+spt_status spt_debug_xq_fused(int32_t device, int32_t dtype, const float* x, const float* ln_w, const float* ln_b,
+                              const float* wq, const float* bias, const float* k, const float* v, float pad_value,
+                              int32_t B, int32_t H, int32_t T_enc, int32_t lds, int32_t touch, float* q, float* out,
+                              char* err, size_t errlen);
 
 /* Quantised decoder weights resident in HBM (additive over ABI 14, announced by
  * SPT_HAS_QUANT_RESIDENT).  spt_debug_qgemv is the decoder GEMV alone over one

@@ -413,6 +413,28 @@ extern "C" {
         err: *mut c_char,
         errlen: usize,
     ) -> spt_status;
+    // the fused cross-Q + cross-attention launch alone (lds: 0..2 staged blocks, touch: 0 or 2)
+    pub fn spt_debug_xq_fused(
+        device: i32,
+        dtype: i32,
+        x: *const f32,
+        ln_w: *const f32,
+        ln_b: *const f32,
+        wq: *const f32,
+        bias: *const f32,
+        k: *const f32,
+        v: *const f32,
+        pad_value: f32,
+        b: i32,
+        h: i32,
+        t_enc: i32,
+        lds: i32,
+        touch: i32,
+        q: *mut f32,
+        out: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
     pub fn spt_get_weight_residency(
         ctx: *const spt_ctx,
         resident_weights: *mut i64,

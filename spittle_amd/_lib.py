@@ -60,7 +60,7 @@ EXPORTS = [
     # the sampler kernels alone (test hooks, additive over ABI 14)
     "spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather",
     # the attention kernels alone (test hooks, additive over ABI 14)
-    "spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross",
+    "spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross", "spt_debug_xq_fused",
     # quantised decoder weights resident in HBM (SPT_HAS_QUANT_RESIDENT)
     "spt_debug_qgemv", "spt_get_weight_residency",
 ]
@@ -428,7 +428,9 @@ def load():
     L.spt_debug_attn_self.argtypes = [i32, i32, fp, fp, i32, i32, i32, i32, i32, fp, C.c_char_p, C.c_size_t]
     L.spt_debug_attn_cross.argtypes = [i32, i32, i32, fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32p,
                                        i32, fp, fp, C.c_char_p, C.c_size_t]
-    for fn in ("spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross"):
+    L.spt_debug_xq_fused.argtypes = [i32, i32, fp, fp, fp, fp, fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, fp, fp,
+                                     C.c_char_p, C.c_size_t]
+    for fn in ("spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross", "spt_debug_xq_fused"):
         getattr(L, fn).restype = C.c_int
     L.spt_debug_qgemv.argtypes = [i32, i32, i32, C.c_void_p, C.c_size_t, i32, i32, fp, i32, fp, fp, fp, fp, i32, i32,
                                   i32, fp, fp, fp, fp, fp, C.c_char_p, C.c_size_t]

@@ -84,3 +84,27 @@ def cross(q, k, v, *, Tq=1, mode="8wave", splits=1, b0=0, B=None, kvrow=None, sh
                                   b0, H, T_enc, Tq, splits, _ptr(km, C.c_int32), share, _ptr(out), _ptr(part), err, 512)
     _check(st, err)
     return part if want_part else out
+
+
+def xq_fused(x, ln_w, ln_b, wq, bias, k, v, *, lds=0, touch=2, pad_value=0.0, dtype="bf16", H=None, device: int = 0):
+    """One fused cross-Q + cross-attention launch (dec_xq_fused): f32 residual rows x [B][1280], LN2
+    (ln_w, ln_b [1280]), the cross-Q projection (wq [1280][1280], bias [1280]) and plain k, v
+    [B][20][T_enc][64], row b on window b.  lds / touch: key blocks per attention wave staged in LDS /
+    touched before q arrives.  -> (q [B][1280], out [B][1280]) as f32."""
+    lib = L.load()
+    f = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    xx, kk, vv = f(x), f(k), f(v)
+    B = xx.shape[0] if xx is not None else kk.shape[0]
+    if H is None:
+        H = kk.shape[1]
+    T_enc = kk.shape[2]
+    if kk.shape != (B, H, T_enc, 64) or (vv is not None and vv.shape != kk.shape):
+        raise ValueError("xq_fused: k and v are [B][H][T_enc][64]")
+    q = np.zeros((max(B, 1), 1280), np.float32)
+    out = np.zeros((max(B, 1), 1280), np.float32)
+    err = C.create_string_buffer(512)
+    st = lib.spt_debug_xq_fused(device, DTYPES[dtype], _ptr(xx), _ptr(f(ln_w)), _ptr(f(ln_b)), _ptr(f(wq)), _ptr(f(bias)),
+                                _ptr(kk), _ptr(vv), float(pad_value), B, H, T_enc, int(lds), int(touch), _ptr(q), _ptr(out),
+                                err, 512)
+    _check(st, err)
+    return q, out

@@ -205,4 +205,85 @@ spt_status spt_debug_attn_cross(int32_t device, int32_t dtype, int32_t mode, con
     }
 }
 
+spt_status spt_debug_xq_fused(int32_t device, int32_t dtype, const float* x, const float* ln_w, const float* ln_b,
+                              const float* wq, const float* bias, const float* k, const float* v, float pad_value,
+                              int32_t B, int32_t H, int32_t T_enc, int32_t lds, int32_t touch, float* q, float* out,
+                              char* err, size_t errlen) {
+    if (!x || !ln_w || !ln_b || !wq || !bias || !k || !v || !q || !out) {
+        set_err(err, errlen, "null argument");
+        return SPT_ERR_INVALID_ARG;
+    }
+    const int d = 1280;
+    try {
+        if (dtype != spt::DT_BF16 && dtype != spt::DT_F16) throw std::runtime_error("debug_xq_fused: dtype is bf16 or f16");
+        if (H != d / 64) throw std::runtime_error("debug_xq_fused: the fused launch is d = 1280, H = 20");
+        if (B < 1 || B > 16) throw std::runtime_error("debug_xq_fused: 1..16 rows");
+        if (T_enc < 256 || T_enc > 1536) throw std::runtime_error("debug_xq_fused: T_enc in 256..1536");
+        if (lds < 0 || lds > 2) throw std::runtime_error("debug_xq_fused: 0..2 staged blocks per wave");
+        if (touch != 0 && touch != 2) throw std::runtime_error("debug_xq_fused: 0 or 2 touched blocks per wave");
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return SPT_ERR_INVALID_ARG;
+    }
+    if (spt_status s = device_ok(device, err, errlen)) return s;
+    try {
+        hipDeviceProp_t prop;
+        HIP_CHECK(hipGetDeviceProperties(&prop, device));
+        if (!spt::dec_xq_fused_ok(dtype, B, d, H, T_enc, prop.multiProcessorCount)) {
+            // (GV_EXACT_LN=0 also lands here: the chain's cross-Q is then another kernel)
+            set_err(err, errlen, "debug_xq_fused: 80 + B * H workgroups are not all resident on this device");
+            return SPT_ERR_INVALID_ARG;
+        }
+        // the layer as the K/V GEMM's epilogue writes it, as spt_debug_attn_cross lays it out
+        const size_t n_kv = (size_t)spt::kv_layer_elems(B, H, T_enc);
+        std::vector<float> lay(n_kv, pad_value);
+        const int T32 = (T_enc + 31) / 32 * 32;
+        for (int kvi = 0; kvi < 2; ++kvi) {
+            const float* src = kvi ? v : k;
+            for (int b = 0; b < B; ++b)
+                for (int h = 0; h < H; ++h)
+                    for (int t = 0; t < T32; ++t) {
+                        float* dst = lay.data() + spt::kv_offset(0, kvi, b, h, t, 0, B, H, T_enc);
+                        if (t < T_enc) memcpy(dst, src + (((size_t)b * H + h) * T_enc + t) * 64, 64 * sizeof(float));
+                    }
+        }
+        const size_t nq = (size_t)B * d, esz = (size_t)spt::dtype_size(dtype);
+        const spt::DecState ds0{0, 0, 0u};
+        std::vector<uint16_t> w16, kv16;
+        Scope sc(device);
+        spt::gemv_prepare(dtype);
+        float* zero = sc.alloc<float>(nq);
+        HIP_CHECK(hipMemsetAsync(zero, 0, nq * sizeof(float), sc.st));
+        unsigned long long* gran = sc.alloc<unsigned long long>(nq);
+        HIP_CHECK(hipMemsetAsync(gran, 0, nq * sizeof(unsigned long long), sc.st));
+        unsigned* werr = sc.alloc<unsigned>(1);
+        HIP_CHECK(hipMemsetAsync(werr, 0, sizeof(unsigned), sc.st));
+        spt::GemvArgs a{};
+        a.A = sc.up(x, nq); a.lda = d; a.R = B;
+        a.ln_w = sc.up(ln_w, (size_t)d); a.ln_b = sc.up(ln_b, (size_t)d);
+        for (int p = 0; p < spt::kMaxPend; ++p) a.pend[p] = zero;
+        a.W = up_as(sc, dtype, wq, (size_t)d * d, w16); a.N = d; a.K = d;
+        a.bias = sc.up(bias, (size_t)d);
+        a.C = sc.out<char>(nq * esz); a.ldc = d;
+        spt::XqFuseArgs xa{};
+        xa.kv = up_as(sc, dtype, lay.data(), n_kv, kv16); xa.B_layout = B; xa.H = H; xa.T_enc = T_enc;
+        xa.out = sc.out<char>(nq * esz); xa.gran = gran; xa.ds = sc.up(&ds0, 1); xa.err = werr; xa.layer = 0;
+        xa.lds = lds; xa.touch = touch;
+        spt::dec_xq_fused(dtype, a, xa, B, sc.st);
+        unsigned herr = 0;
+        sc.down(&herr, (const unsigned*)werr, 1);
+        down_f32(sc, dtype, a.C, q, nq);
+        down_f32(sc, dtype, xa.out, out, nq);
+        sc.sync();
+        if (herr) {  // never retried: the caller sees the wait that ran out
+            set_err(err, errlen, "debug_xq_fused: a consumer's wait for q ran out");
+            return SPT_ERR_DEVICE;
+        }
+        return SPT_OK;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return spt_classify(e);
+    }
+}
+
 }  // extern "C"

@@ -208,6 +208,48 @@ struct AttnWave {
             process(kc_[i % PF], vc_[i % PF], (blk + i * NW) * KB, qv, lim, Tq);
         }
     }
+    // ring_run with blocks 2 .. 2 + NS - 1 of the wave's schedule staged in LDS by another wave and the others
+    // through the ring, in two halves around the barrier that orders the staged bytes (the caller's).
+    // staged_head processes blocks 0 and 1 (ring_fill's) and requests the next two ring blocks, 2 + NS and
+    // 3 + NS; staged_tail copies each staged block into the ring slot block 1 has left and processes it,
+    // then runs the ring to its end.  Same blocks in the same order through the same process(): ring_run's
+    // bits.  st: the wave's staged blocks at the lane's 16 bytes; block s holds K piece i at
+    // s * 8 KiB + i KiB and V piece i 4 KiB further, each lane-linear with load_blk's lanes.
+    template <int MAXB, int NS>
+    __device__ __forceinline__ void staged_head(int blk, int nblk, const float (&qv)[NQ][8], const int (&lim)[NQ], int Tq) {
+        static_assert(PF == 3 && NI == 4 && sizeof(T) == 2 && NS >= 1 && 2 + NS <= MAXB && MAXB <= 8,
+                      "AttnWave: the staged schedule is the fused launch's");
+        const int cnt = blk < nblk ? (nblk - 1 - blk) / NW + 1 : 0;
+        const int mine = blk + (max(cnt, 1) - 1) * NW;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {  // no early exit: every wave goes on to the barrier
+            if (p + 2 < MAXB - NS) load_blk(kc_[(p + 2) % PF], vc_[(p + 2) % PF], min(blk + (p + 2 + NS) * NW, mine));
+            if (p < cnt) process(kc_[p], vc_[p], (blk + p * NW) * KB, qv, lim, Tq);
+        }
+    }
+    template <int MAXB, int NS>
+    __device__ __forceinline__ void staged_tail(int blk, int nblk, const float (&qv)[NQ][8], const int (&lim)[NQ], int Tq,
+                                                const char* st) {
+        if (blk >= nblk) return;
+        const int cnt = (nblk - 1 - blk) / NW + 1;
+        const int mine = blk + (cnt - 1) * NW;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            if (2 + s >= cnt) return;
+#pragma unroll
+            for (int i = 0; i < NI; ++i) {
+                kc_[1][i].load((const T*)(st + s * 8192 + i * 1024));
+                vc_[1][i].load((const T*)(st + s * 8192 + 4096 + i * 1024));
+            }
+            process(kc_[1], vc_[1], (blk + (2 + s) * NW) * KB, qv, lim, Tq);
+        }
+#pragma unroll
+        for (int p = 2; p < MAXB - NS; ++p) {  // ring position p is block p + NS of the schedule
+            if (p + NS >= cnt) return;
+            if (p + 2 < MAXB - NS) load_blk(kc_[(p + 2) % PF], vc_[(p + 2) % PF], min(blk + (p + 2 + NS) * NW, mine));
+            process(kc_[p % PF], vc_[p % PF], (blk + (p + NS) * NW) * KB, qv, lim, Tq);
+        }
+    }
     // sum l and o over the 8 key slots of the wave (m is wave-uniform) into LDS
     __device__ __forceinline__ void to_lds(float (*s_m)[NQ], float (*s_l)[NQ], float (*s_o)[NQ][64], int wid,
                                            int lane) {

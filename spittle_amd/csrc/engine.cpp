@@ -1075,7 +1075,7 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
             if (np != 0) throw std::runtime_error("fused cross-Q launch: pending slabs before LN2");
             XqFuseArgs x{};
             x.kv = ckv_l; x.B_layout = E; x.H = H; x.T_enc = T; x.out = g.dao; x.gran = g.xq_gran; x.ds = g.ds;
-            x.err = xq_err_; x.layer = l;
+            x.err = xq_err_; x.layer = l; x.lds = xq_lds_; x.touch = xq_touch_;
             dec_xq_fused(dt_, a, x, B, st);
         } else {
             gemv(dt_, GV_BIAS, A_LN, a, st);
@@ -1418,7 +1418,7 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
             // into the cross-attention grid (the map itself is read from g->kvrow)
             GraphKey key{g->B, E, g->b0, out_cap, rq.n_forced, rq.flags, rq.full};
             key.share = S;
-            key.fuse = xq_on_;
+            key.fuse = xq_on_ ? 1 + xq_lds_ + 4 * xq_touch_ : 0;
             auto it = g->graphs.find(key);
             if (it == g->graphs.end()) {
                 hipGraph_t graph;
@@ -1473,6 +1473,12 @@ void Engine::decode(int B, const DecodeRequest& rq, int* tokens, float* top1, fl
     // beam search continues from the host step by step with no such check: it stays on the chain.
     const char* xq_env = getenv("SPT_XQ_FUSE");
     xq_on_ = rq.beam_k == 0 && !(xq_env && atoi(xq_env) == 0);
+    // SPT_XQ_LDS=0|1|2, SPT_XQ_TOUCH=0|2: the fused launch's staged and touched blocks (A/B; no result
+    // changes), read and applied as SPT_XQ_FUSE is
+    const char* lds_env = getenv("SPT_XQ_LDS");
+    xq_lds_ = lds_env ? std::min(2, std::max(0, atoi(lds_env))) : kXqLdsDefault;
+    const char* touch_env = getenv("SPT_XQ_TOUCH");
+    xq_touch_ = touch_env ? (atoi(touch_env) != 0 ? 2 : 0) : kXqTouchDefault;
     struct XqOff {
         bool& on;
         ~XqOff() { on = false; }

@@ -159,7 +159,9 @@ private:
         uint32_t flags;
         bool full;
         int share = 0;  // rows per window (0: identity rows, no window map)
-        bool fuse = false;  // captured while the fused cross-Q + cross-attention launch was allowed (xq_on_)
+        // 0, or captured while the fused cross-Q + cross-attention launch was allowed (xq_on_): 1 + its
+        // staged blocks + 4 x its touched blocks (SPT_XQ_LDS, SPT_XQ_TOUCH)
+        int fuse = 0;
         bool operator<(const GraphKey& o) const {
             if (full != o.full) return full < o.full;
             if (fuse != o.fuse) return fuse < o.fuse;
@@ -251,6 +253,7 @@ private:
     // leaves their launch count in xq_enq_ (added to the call's statistics at once when eager, per
     // replay when captured).  xq_err_: the device word a consumer sets when it gives up waiting.
     bool xq_on_ = false;
+    int xq_lds_ = kXqLdsDefault, xq_touch_ = kXqTouchDefault;  // SPT_XQ_LDS, SPT_XQ_TOUCH as decode() read them
     int xq_enq_ = 0;
     int n_cu_ = 0;
     unsigned* xq_err_ = nullptr;

@@ -43,8 +43,18 @@ void set_xattn_stamp(void* p) { HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_xattn_s
         if (g_xattn_stamp && threadIdx.x == 0)                                               \
             g_xattn_stamp[3 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime();          \
     } while (0)
+// and of the fused cross-Q + cross-attention launch: per workgroup {entry, q seen, staged blocks
+// ready, streaming done, exit} (producers: entry and exit only), thread 0's view
+__device__ unsigned long long* g_xq_stamp;
+void set_xq_stamp(void* p) { HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_xq_stamp), &p, sizeof(p))); }
+#define XQ_STAMP(i)                                                                          \
+    do {                                                                                     \
+        if (g_xq_stamp && threadIdx.x == 0)                                                  \
+            g_xq_stamp[5 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime();             \
+    } while (0)
 #else
 #define XA_STAMP(i) do {} while (0)
+#define XQ_STAMP(i) do {} while (0)
 #endif
 
 namespace {
@@ -191,14 +201,27 @@ __global__ __launch_bounds__(64 * NW) void cross_attn_kernel(const T* __restrict
 // 128 bytes: one line per lane, one load instruction, one register); the ring's own loads of those
 // blocks, issued once q is there, then find the lines in flight or in L2.
 // QW: the cross-Q matrix is resident in its packed ggml blocks (gemv_body's quantised fetch).
-template <typename T, int TOUCH, bool QW = false, int PF = 3>
+// LDSB: the blocks number 2 .. 2 + LDSB - 1 of every attention wave's schedule are staged
+// in LDS by the tenth wave, which requests them at launch by LDS-DMA (no register destination, every byte
+// fetched once): block s of wave w at kXqStage + (w * LDSB + s) * 8 KiB, four K pieces then four V
+// pieces of 1 KiB, each lane-linear with load_blk's per-lane source, so that lane L's ds_read_b128 at
+// piece + 16 L returns the 16 bytes load_blk would have put in its registers.  The attention waves
+// issue no LDS-DMA themselves (their ring's counted waits stay counted) and read the staged blocks only
+// past a barrier that the loader reaches after its vmcnt(0): nothing else orders a ds_read behind
+// another wave's LDS-DMA.  The loader shares the q hand-off barrier (every live wave must arrive at every
+// barrier) without waiting for its DMA there, takes the give-up path with the others, and drains its
+// DMA before it ends on either path.  LDSB = 0 is the kernel without any of this.
+constexpr int kXqStage = 4096;  // the consumer's merge scratch, q bits and s_ok live below (2244 bytes)
+template <typename T, int TOUCH, bool QW = false, int LDSB = 0, int PF = 3>
 __global__ __launch_bounds__(640) void xq_fused_kernel(GemvArgs a, XqFuseArgs x) {
     const int n_prod = a.N / 16;
     // a vector load: a scalar one would hold every workgroup's first kernel-argument wait for its round trip
     const unsigned tag =
         (__hip_atomic_load(&x.ds->epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + 1u) * 64u + (unsigned)x.layer;
+    XQ_STAMP(0);
     if ((int)blockIdx.x < n_prod) {
         gemv_body<T, GV_BIAS, LN_SRC(0), 1, 10, 1, 1, true, true, QW>(a, x.gran, tag);
+        XQ_STAMP(4);
         return;
     }
     typedef AttnWave<T, 1, 0, AW, PF> W;
@@ -212,8 +235,37 @@ __global__ __launch_bounds__(640) void xq_fused_kernel(GemvArgs a, XqFuseArgs x)
     int* s_ok = (int*)(smem + AW * 256 + AW * 8 + 128);
     const int cb = (int)blockIdx.x - n_prod, j = cb / x.H, h = cb - j * x.H;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, g = lane & 7;
-    if (wid > AW) return;  // the producer geometry's tenth wave has no part here
     const int nblk = cdiv(x.T_enc, W::KB);
+    if (wid > AW) {  // the producer geometry's tenth wave: the LDS loader, or no part here
+        if constexpr (LDSB > 0) {
+            typedef const __attribute__((address_space(1))) void* GP;
+            typedef __attribute__((address_space(3))) void* LP;
+            const T* kb = (const T*)x.kv + ((size_t)j * x.H + h) * 4096 + 8 * g;
+            const int bstride = x.B_layout * x.H * 4096, slot = lane >> 3;
+#pragma unroll
+            for (int s = 0; s < LDSB; ++s) {
+#pragma unroll
+                for (int w = 0; w < AW; ++w) {
+                    const int mine = w + (nblk - 1 - w) / AW * AW;  // wave w's last block (nblk >= AW)
+                    const int blk = min(w + (2 + s) * AW, mine);    // ring_run's clamp
+#pragma unroll
+                    for (int i = 0; i < W::NI; ++i) {  // load_blk's addresses
+                        const int key = min(blk * W::KB + 8 * i + slot, x.T_enc - 1);
+                        const uint32_t off = (uint32_t)((key >> 5) * bstride + (key & 31) * 64);
+                        char* dst = smem + kXqStage + ((w * LDSB + s) * 8 + i) * 1024;
+                        __builtin_amdgcn_global_load_lds((GP)(kb + off), (LP)dst, 16, 0, 0);
+                        __builtin_amdgcn_global_load_lds((GP)(kb + 2048 + off), (LP)(dst + 4096), 16, 0, 0);
+                    }
+                }
+            }
+            // the q hand-off barrier, raw: a __syncthreads() here would wait for the DMA first
+            asm volatile("s_barrier" ::: "memory");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every staged byte is in LDS (and none lands later)
+            // the staged blocks' barrier, unless wave 8 gave up (the attention waves then end without it)
+            if (__builtin_amdgcn_readfirstlane(*s_ok)) asm volatile("s_barrier" ::: "memory");
+        }
+        return;
+    }
     W aw;
     unsigned touch[TOUCH > 0 ? TOUCH : 1] = {};
     if (wid < AW) {
@@ -251,6 +303,7 @@ __global__ __launch_bounds__(640) void xq_fused_kernel(GemvArgs a, XqFuseArgs x)
     }
     __syncthreads();
     if (wid >= AW || !*s_ok) return;
+    XQ_STAMP(1);
     float qv[1][8];
     int lim[1] = {x.T_enc};
 #pragma unroll
@@ -259,7 +312,17 @@ __global__ __launch_bounds__(640) void xq_fused_kernel(GemvArgs a, XqFuseArgs x)
         __builtin_memcpy(&qt, &s_q[8 * g + e], 2);
         qv[0][e] = to_f<T>(qt) * kLog2Scale;
     }
-    aw.template ring_run<MAXB>(wid, nblk, qv, lim, 1);
+    if constexpr (LDSB > 0) {
+        aw.template staged_head<MAXB, LDSB>(wid, nblk, qv, lim, 1);
+        // the staged blocks' barrier: the loader arrives behind its vmcnt(0).  Raw, and reached by all 8
+        // waves whatever their block counts; these waves have written nothing the others wait for.
+        asm volatile("s_barrier" ::: "memory");
+        XQ_STAMP(2);
+        aw.template staged_tail<MAXB, LDSB>(wid, nblk, qv, lim, 1, smem + kXqStage + wid * LDSB * 8192 + lane * 16);
+    } else {
+        aw.template ring_run<MAXB>(wid, nblk, qv, lim, 1);
+    }
+    XQ_STAMP(3);
     aw.to_lds(s_m, s_l, s_o, wid, lane);
     __syncthreads();
     if (tid < 64) {
@@ -267,6 +330,7 @@ __global__ __launch_bounds__(640) void xq_fused_kernel(GemvArgs a, XqFuseArgs x)
         attn_merge<1, AW>(s_m, s_l, s_o, 0, tid, M, L, O);
         ((T*)x.out)[((size_t)j * x.H + h) * 64 + tid] = from_f<T>(O / L);
     }
+    XQ_STAMP(4);
     if constexpr (TOUCH > 0) {
         // the touched dwords are used nowhere; this keeps their loads (layer is never negative)
         unsigned u = 0;
@@ -438,6 +502,7 @@ __global__ void reset_kernel(DecState* ds, unsigned* arrive) {
 }  // namespace
 
 void gemv_prepare(int dtype) {
+    dec_xq_fused_prepare(dtype);
     if (dtype == DT_BF16) gemv_attr_modes<bf16>();
     else if (dtype == DT_F16) gemv_attr_modes<f16>();
     else gemv_attr_modes<float>();
@@ -605,6 +670,34 @@ void dec_cross_attn_vw(int dtype, const void* q, const void* kv, int B, int B_la
     SPT_LAUNCH_CHECK();
 }
 
+namespace {
+// the fused launch's instances by {touched blocks 0 / 2, packed cross-Q weights, staged blocks 0..2}
+typedef void (*XqKernel)(GemvArgs, XqFuseArgs);
+template <typename T>
+XqKernel xq_kernel(int touch, bool qw, int ldsb) {
+#define SPT_XQ_L(TO, QW) {xq_fused_kernel<T, TO, QW, 0>, xq_fused_kernel<T, TO, QW, 1>, xq_fused_kernel<T, TO, QW, 2>}
+    static const XqKernel tab[2][2][3] = {{SPT_XQ_L(0, false), SPT_XQ_L(0, true)}, {SPT_XQ_L(2, false), SPT_XQ_L(2, true)}};
+#undef SPT_XQ_L
+    return tab[touch ? 1 : 0][qw ? 1 : 0][ldsb];
+}
+// dynamic LDS of every workgroup of the launch: the producers' LayerNorm image and reduction, or the
+// consumers' scratch and staged blocks (8 waves x ldsb x 8 KiB)
+int xq_lds_bytes(int R, int K, int ldsb) {
+    const int prod = std::max(4096, gv_img_bytes(R, K, 2) + 10 * 64 * (int)sizeof(f32x4));
+    return std::max(prod, ldsb > 0 ? kXqStage + AW * ldsb * 8192 : 0);
+}
+}  // namespace
+
+// the staged instances take more than 64 KiB of dynamic LDS: enabled per kernel, outside any stream capture
+void dec_xq_fused_prepare(int dtype) {
+    if (dtype_size(dtype) != 2) return;
+    for (int touch = 0; touch <= 2; touch += 2)
+        for (int qw = 0; qw < 2; ++qw)
+            for (int l = 1; l <= 2; ++l)
+                ensure_lds_attr((const void*)(dtype == DT_BF16 ? xq_kernel<bf16>(touch, qw, l) : xq_kernel<f16>(touch, qw, l)),
+                                xq_lds_bytes(16, 1280, l));
+}
+
 bool dec_xq_fused_ok(int dtype, int B, int d, int H, int T_enc, int n_cu) {
     // the chain's cross-Q must be the exact 10-wave GEMV (GV_EXACT_LN=0 gives it another K order)
     static const bool exact_ln = !getenv("GV_EXACT_LN") || atoi(getenv("GV_EXACT_LN")) != 0;
@@ -623,26 +716,13 @@ void dec_xq_fused(int dtype, const GemvArgs& cq, const XqFuseArgs& x, int B, hip
         throw std::runtime_error("dec_xq_fused: a layer's cross K/V exceeds 2^31 elements");
     GemvArgs a = cq;
     a.ksplit = 1;
-    const int lds = std::max(4096, gv_img_bytes(a.R, a.K, 2) + 10 * 64 * (int)sizeof(f32x4));
+    if (x.lds < 0 || x.lds > 2 || (x.touch != 0 && x.touch != 2))
+        throw std::runtime_error("dec_xq_fused: 0..2 staged blocks, 0 or 2 touched blocks");
     const dim3 grid(a.N / 16 + B * x.H), blk(640);
-    // SPT_XQ_TOUCH=0: no touched blocks beyond the ring (A/B; no result changes).  Default 2; touching all
-    // four remaining blocks measured as slow as the two launches (profiles/r7/exp_xq_fuse.txt)
-    static const bool touch = !getenv("SPT_XQ_TOUCH") || atoi(getenv("SPT_XQ_TOUCH")) != 0;
     QPackGeom qg;
     if (a.wq && !qpack_geom(a.wq, &qg)) throw std::runtime_error("dec_xq_fused: no resident layout for this weight type");
-#define SPT_XQ(T, TOUCH) \
-    do { \
-        if (a.wq) hipLaunchKernelGGL((xq_fused_kernel<T, TOUCH, true>), grid, blk, lds, st, a, x); \
-        else hipLaunchKernelGGL((xq_fused_kernel<T, TOUCH>), grid, blk, lds, st, a, x); \
-    } while (0)
-    if (dtype == DT_BF16) {
-        if (touch) SPT_XQ(bf16, 2);
-        else SPT_XQ(bf16, 0);
-    } else {
-        if (touch) SPT_XQ(f16, 2);
-        else SPT_XQ(f16, 0);
-    }
-#undef SPT_XQ
+    const XqKernel k = dtype == DT_BF16 ? xq_kernel<bf16>(x.touch, a.wq != 0, x.lds) : xq_kernel<f16>(x.touch, a.wq != 0, x.lds);
+    hipLaunchKernelGGL(k, grid, blk, xq_lds_bytes(a.R, a.K, x.lds), st, a, x);
     SPT_LAUNCH_CHECK();
 }
 

@@ -70,6 +70,7 @@ void fill_f32(float* dst, int64_t n, float v, hipStream_t st);
 void ggml_dequant(int type, const void* src, int64_t n, int out_dtype, void* dst, hipStream_t st);
 void cache_flush(const void* p, int64_t bytes, unsigned* sink, hipStream_t st);
 void set_xattn_stamp(void* p);
+void set_xq_stamp(void* p);  // SPT_STAMP=1 builds only: [workgroups][5] of the fused cross-Q launch
 void dec_cross_attn_ni8(const void* q, const void* kv, int B, int B_layout, int H, int T_enc, void* out, int blocked,
                         hipStream_t st);  // ubench variant  // SPT_STAMP=1 builds only (ubench)
 void stream_read(const void* p, int64_t bytes, unsigned* sink, int grid, int tpb, hipStream_t st);  // ubench probe
@@ -217,12 +218,18 @@ struct XqFuseArgs {
     const DecState* ds;
     unsigned* err;
     int layer;                               // < 64
+    int lds = 0;                             // key blocks per attention wave staged in LDS by the loader wave: 0..2
+    int touch = 2;                           // key blocks per wave touched (one dword per line) before q: 0 or 2
 };
+// what the engine runs unless SPT_XQ_LDS / SPT_XQ_TOUCH say otherwise
+constexpr int kXqLdsDefault = 1, kXqTouchDefault = 0;
 constexpr long long kXqTimeoutTicks = 2000000;  // 20 ms against a hand-off of microseconds
 // whether the shapes are the fused launch's (host): 16-bit dtype, one query per row, the exact
 // 10-wave cross-Q geometry (K = 1280), 1500-key class windows, and every workgroup resident at once
 bool dec_xq_fused_ok(int dtype, int B, int d, int H, int T_enc, int n_cu);
 void dec_xq_fused(int dtype, const GemvArgs& cq, const XqFuseArgs& x, int B, hipStream_t st);
+// one-time per-process kernel attributes of the staged instances (gemv_prepare calls it)
+void dec_xq_fused_prepare(int dtype);
 
 // the 8 partials of each of R query rows x H heads merged into out [R][H * 64] (bitwise the 8-wave
 // kernel's output), for a plain (A_DIRECT) cross output projection

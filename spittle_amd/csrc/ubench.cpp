@@ -3,6 +3,8 @@
 //   ubench gemv  N K R mode ln dtype [ksplit npend]  mode: 0 bias 1 gelu 2 partial 3 qkv 4 logits 5 resid
 //   ubench attn  B H ctx nkeys Tq dtype   self-attention
 //   ubench xattn B T splits dtype        cross-attention, 8 layers back to back
+//   ubench xqfused B T lds touch dtype   fused cross-Q + cross-attention, 8 layers back to back
+//                                        (SPT_STAMP builds: the workgroup timeline of one launch)
 //   ubench gemm  M N K epi dtype         128 vs 256 tile (time, bitwise diff)
 //   ubench layer B dtype [xsplit]        one large-v3 decoder layer (8 launches)
 //   ubench layer2 B dtype [...]          two such chains on two streams
@@ -324,6 +326,81 @@ int main(int argc, char** argv) {
 #endif
         printf("cross-attn B=%d T=%d splits=%d dt=%d (8 layers back to back) : %.2f us  %.0f GB/s\n", B, T, S, dt, us,
                2.0 * B * H * T * 64 * esz / us / 1e3);
+        return 0;
+    }
+    if (what == "xqfused") {
+        // the fused cross-Q + cross-attention launch of NL layers back to back, each on
+        // its own weights and K/V (cache-cold), lds staged and touch touched key blocks per wave; an
+        // advance launch ends each round of NL so that the next round's hand-off tags are new
+        const int B = ai(2, 8), T = ai(3, 1500), lds = ai(4, 0), touch = ai(5, 2), dt = ai(6, DT_BF16), NL = 8, d = 1280, H = 20;
+        const int esz = dtype_size(dt);
+        gemv_prepare(dt);
+        const size_t layer = (size_t)2 * B * H * ((T + 31) / 32 * 32) * 64;
+        void* kv = drand(layer * NL, dt, 2, 0);
+        void* W = drand((size_t)d * d * NL, dt, 3, -5);
+        float* bias = frand(d, 4, -5);
+        float* lnw = frand(d, 5, -3);
+        float* lnb = frand(d, 6, -4);
+        float* x = frand((size_t)B * d, 7, 0);
+        float* zero = (float*)dalloc((size_t)B * d * 4);
+        void* q = dalloc((size_t)B * d * esz);
+        void* out = dalloc((size_t)B * d * esz);
+        unsigned long long* gran = (unsigned long long*)dalloc((size_t)B * d * 8);
+        unsigned* err = (unsigned*)dalloc(64);
+        auto launch = [&](int l) {
+            GemvArgs a{};
+            a.A = x; a.lda = d; a.R = B; a.ln_w = lnw; a.ln_b = lnb;
+            for (int p = 0; p < kMaxPend; ++p) a.pend[p] = zero;
+            a.W = (const char*)W + (size_t)d * d * l * esz; a.N = d; a.K = d; a.bias = bias; a.C = q; a.ldc = d;
+            XqFuseArgs xa{};
+            xa.kv = (const char*)kv + layer * l * esz; xa.B_layout = B; xa.H = H; xa.T_enc = T; xa.out = out; xa.gran = gran;
+            xa.ds = ds; xa.err = err; xa.layer = l; xa.lds = lds; xa.touch = touch;
+            dec_xq_fused(dt, a, xa, B, st);
+        };
+        HIP_CHECK(hipDeviceSynchronize());
+        const double us = time_us(st, 10, [&] {
+            for (int l = 0; l < NL; ++l) launch(l);
+            dec_advance(ds, 1, st);
+        }) / NL;
+#if SPT_STAMP
+        {   // workgroup timeline of one more (cache-cold) launch
+            const int n_prod = d / 16, nwg = n_prod + B * H;
+            unsigned long long* sp = (unsigned long long*)dalloc((size_t)nwg * 5 * 8);
+            void* flush = dalloc((size_t)512 << 20);
+            unsigned* sink = (unsigned*)dalloc(64);
+            cache_flush(flush, (int64_t)512 << 20, sink, st);
+            HIP_CHECK(hipStreamSynchronize(st));
+            set_xq_stamp(sp);
+            launch(0);
+            HIP_CHECK(hipStreamSynchronize(st));
+            set_xq_stamp(nullptr);
+            std::vector<unsigned long long> h((size_t)nwg * 5);
+            HIP_CHECK(hipMemcpy(h.data(), sp, h.size() * 8, hipMemcpyDeviceToHost));
+            unsigned long long t0 = ~0ull;
+            for (int i = 0; i < nwg; ++i) t0 = std::min(t0, h[5 * i]);
+            auto q3 = [&](int w0, int w1, int k) {  // min / median / max over workgroups [w0, w1) of stamp k
+                std::vector<double> v;
+                for (int i = w0; i < w1; ++i)
+                    if (h[5 * i + k]) v.push_back((h[5 * i + k] - t0) * 0.01);
+                char b[128] = "-";
+                if (!v.empty()) {
+                    std::sort(v.begin(), v.end());
+                    snprintf(b, sizeof b, "%.2f / %.2f / %.2f", v.front(), v[v.size() / 2], v.back());
+                }
+                return std::string(b);
+            };
+            printf("  timeline, us from the first workgroup's entry (min / median / max over workgroups):\n");
+            printf("    producers (%d): entry %s | exit %s\n", n_prod, q3(0, n_prod, 0).c_str(), q3(0, n_prod, 4).c_str());
+            printf("    consumers (%d): entry %s | q seen %s | staged blocks ready %s | streamed %s | exit %s\n", B * H,
+                   q3(n_prod, nwg, 0).c_str(), q3(n_prod, nwg, 1).c_str(), q3(n_prod, nwg, 2).c_str(),
+                   q3(n_prod, nwg, 3).c_str(), q3(n_prod, nwg, 4).c_str());
+        }
+#endif
+        unsigned herr = 0;
+        HIP_CHECK(hipMemcpy(&herr, err, 4, hipMemcpyDeviceToHost));
+        printf("xq-fused B=%d T=%d lds=%d touch=%d dt=%d (8 layers back to back, one advance per 8) : %.2f us  %.0f GB/s%s\n",
+               B, T, lds, touch, dt, us, (2.0 * B * H * T * 64 + (double)d * d) * esz / us / 1e3,
+               herr ? "  [a consumer's wait ran out]" : "");
         return 0;
     }
     if (what == "gemm") {  // 128 x 128 vs 256 x 256 tile: timing and bitwise agreement
