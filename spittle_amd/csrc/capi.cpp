@@ -26,18 +26,13 @@
 
 using spt::Engine;
 
+#include "capi_err.h"
 #include "capi_internal.h"
 
 namespace {
+using spt::set_err;
 
 constexpr int kWindow = 480000;
-
-void set_err(char* buf, size_t len, const std::string& msg) {
-    if (buf && len) {
-        strncpy(buf, msg.c_str(), len - 1);
-        buf[len - 1] = 0;
-    }
-}
 
 }  // namespace
 

@@ -3,24 +3,18 @@
 // of one call, and the host rounding of f32 inputs to an engine dtype.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <string.h>
-
 #include <string>
 #include <vector>
 
 #include "../../include/spittle_hip.h"
+#include "capi_err.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace spt {
 namespace dbg {
 
-inline void set_err(char* buf, size_t len, const std::string& m) {
-    if (buf && len) {
-        strncpy(buf, m.c_str(), len - 1);
-        buf[len - 1] = 0;
-    }
-}
+using spt::set_err;
 
 // the calling thread's device and a stream on it, with every buffer the call allocates
 struct Scope {

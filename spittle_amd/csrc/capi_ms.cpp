@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/spittle_hip.h"
+#include "capi_err.h"
 #include "common.h"
 #include "moonshine.h"
 
@@ -25,24 +26,10 @@ struct spt_ms_ctx {
 
 namespace {
 
-spt_status fail(spt_ms_ctx* c, spt_status s, const std::string& m) {
-    if (c) c->err = m;
-    return s;
-}
-
-spt_status classify(const std::exception& e) {
-    if (dynamic_cast<const spt::HipError*>(&e)) return SPT_ERR_DEVICE;
-    if (dynamic_cast<const std::bad_alloc*>(&e)) return SPT_ERR_OOM;
-    if (std::string(e.what()).find("out of device memory") != std::string::npos) return SPT_ERR_OOM;
-    return SPT_ERR_INVALID_ARG;
-}
-
-void set_err(char* buf, size_t len, const std::string& m) {
-    if (buf && len) {
-        strncpy(buf, m.c_str(), len - 1);
-        buf[len - 1] = 0;
-    }
-}
+using spt::classify;
+using spt::fail;
+using spt::guarded;
+using spt::set_err;
 
 spt_ms_result* make_result(const spt_ms_ctx* c, const spt::MsUtt& r) {
     spt_ms_result* o = (spt_ms_result*)calloc(1, sizeof(spt_ms_result));
@@ -162,12 +149,10 @@ spt_status spt_moonshine_tensor_numel(const spt_ms_ctx* ctx, const char* name, i
 
 spt_status spt_moonshine_set_tensor(spt_ms_ctx* ctx, const char* name, const float* data, int64_t n) {
     if (!ctx || !name || !data) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->set_tensor(name, data, n);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 int32_t spt_moonshine_missing_tensors(const spt_ms_ctx* ctx) { return ctx ? ctx->eng->missing() : -1; }
@@ -197,7 +182,7 @@ spt_status spt_moonshine_transcribe_batch(spt_ms_ctx* ctx, const float* const* p
                         " samples is longer than max_samples = " + std::to_string(e.max_samples()));
     }
     e.clear_timings();
-    try {
+    return guarded(ctx, [&]() -> spt_status {
         std::vector<spt::MsUtt> acc(batch);
         std::vector<size_t> live;  // utterances with at least one encoder frame
         for (size_t u = 0; u < batch; u++)
@@ -229,9 +214,7 @@ spt_status spt_moonshine_transcribe_batch(spt_ms_ctx* ctx, const float* const* p
             }
         }
         return SPT_OK;
-    } catch (const std::exception& ex) {
-        return fail(ctx, classify(ex), ex.what());
-    }
+    });
 }
 
 spt_status spt_moonshine_transcribe(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples,
@@ -267,23 +250,19 @@ static spt_status debug_common(spt_ms_ctx* ctx, const float* pcm, size_t n, cons
 spt_status spt_moonshine_debug_stem(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples, float* out) {
     const spt_status s = debug_common(ctx, pcm16k, n_samples, out);
     if (s != SPT_OK) return s;
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->debug_encode(pcm16k, n_samples, false, out);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 spt_status spt_moonshine_debug_encode(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples, float* out) {
     const spt_status s = debug_common(ctx, pcm16k, n_samples, out);
     if (s != SPT_OK) return s;
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->debug_encode(pcm16k, n_samples, true, out);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 spt_status spt_moonshine_debug_logits(spt_ms_ctx* ctx, const float* pcm16k, size_t n_samples, const int32_t* prefix,
@@ -291,12 +270,10 @@ spt_status spt_moonshine_debug_logits(spt_ms_ctx* ctx, const float* pcm16k, size
     const spt_status s = debug_common(ctx, pcm16k, n_samples, out);
     if (s != SPT_OK) return s;
     if (!prefix) return fail(ctx, SPT_ERR_INVALID_ARG, "null prefix");
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->debug_logits(pcm16k, n_samples, prefix, n_prefix, out);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 }  // extern "C"

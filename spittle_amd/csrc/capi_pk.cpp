@@ -17,12 +17,14 @@
 #include <vector>
 
 #include "../../include/spittle_hip.h"
+#include "capi_err.h"
 #include "common.h"
 #include "kernels.h"
 #include "parakeet.h"
 #include "pk_onnx.h"
 
 namespace {
+using spt::set_err;
 constexpr int64_t kMaxGrowBytes = 96ll << 30;  // workspace a long recording may grow to (of 288 GB HBM)
 }
 
@@ -52,13 +54,6 @@ spt_status classify(const std::exception& e) {
     if (dynamic_cast<const spt::PkUnsupported*>(&e)) return SPT_ERR_UNSUPPORTED;
     if (std::string(e.what()).find("out of device memory") != std::string::npos) return SPT_ERR_OOM;
     return SPT_ERR_INVALID_ARG;
-}
-
-void set_err(char* buf, size_t len, const std::string& m) {
-    if (buf && len) {
-        strncpy(buf, m.c_str(), len - 1);
-        buf[len - 1] = 0;
-    }
 }
 
 const char kWordMark[] = "\xE2\x96\x81";  // U+2581, SentencePiece's word-start marker

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/spittle_hip.h"
+#include "capi_err.h"
 #include "common.h"
 #include "sensevoice.h"
 
@@ -25,24 +26,10 @@ struct spt_sv_ctx {
 
 namespace {
 
-spt_status fail(spt_sv_ctx* c, spt_status s, const std::string& m) {
-    if (c) c->err = m;
-    return s;
-}
-
-spt_status classify(const std::exception& e) {
-    if (dynamic_cast<const spt::HipError*>(&e)) return SPT_ERR_DEVICE;
-    if (dynamic_cast<const std::bad_alloc*>(&e)) return SPT_ERR_OOM;
-    if (std::string(e.what()).find("out of device memory") != std::string::npos) return SPT_ERR_OOM;
-    return SPT_ERR_INVALID_ARG;
-}
-
-void set_err(char* buf, size_t len, const std::string& m) {
-    if (buf && len) {
-        strncpy(buf, m.c_str(), len - 1);
-        buf[len - 1] = 0;
-    }
-}
+using spt::classify;
+using spt::fail;
+using spt::guarded;
+using spt::set_err;
 
 spt_sv_result* make_result(const spt_sv_ctx* c, const spt::SvUtt& r) {
     spt_sv_result* o = (spt_sv_result*)calloc(1, sizeof(spt_sv_result));
@@ -195,24 +182,20 @@ spt_status spt_sensevoice_tensor_numel(const spt_sv_ctx* ctx, const char* name, 
 
 spt_status spt_sensevoice_set_tensor(spt_sv_ctx* ctx, const char* name, const float* data, int64_t n) {
     if (!ctx || !name || !data) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->set_tensor(name, data, n);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 int32_t spt_sensevoice_missing_tensors(const spt_sv_ctx* ctx) { return ctx ? ctx->eng->missing() : -1; }
 
 spt_status spt_sensevoice_set_cmvn(spt_sv_ctx* ctx, const float* neg_mean, const float* inv_std, int32_t n) {
     if (!ctx || !neg_mean || !inv_std) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->set_cmvn(neg_mean, inv_std, n);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 spt_status spt_sensevoice_set_vocab(spt_sv_ctx* ctx, const char* const* pieces, int32_t n) {
@@ -242,7 +225,7 @@ spt_status spt_sensevoice_transcribe_batch(spt_sv_ctx* ctx, const float* const* 
                         " samples is longer than max_samples = " + std::to_string(e.max_samples()));
     }
     e.clear_timings();
-    try {
+    return guarded(ctx, [&]() -> spt_status {
         std::vector<spt::SvUtt> acc(batch);
         std::vector<size_t> live;  // utterances with at least one fbank frame
         for (size_t u = 0; u < batch; u++)
@@ -272,9 +255,7 @@ spt_status spt_sensevoice_transcribe_batch(spt_sv_ctx* ctx, const float* const* 
             }
         }
         return SPT_OK;
-    } catch (const std::exception& ex) {
-        return fail(ctx, classify(ex), ex.what());
-    }
+    });
 }
 
 spt_status spt_sensevoice_transcribe(spt_sv_ctx* ctx, const float* pcm16k, size_t n_samples,
@@ -311,12 +292,10 @@ static spt_status debug_common(spt_sv_ctx* ctx, const float* pcm, size_t n, cons
 spt_status spt_sensevoice_debug_features(spt_sv_ctx* ctx, const float* pcm16k, size_t n_samples, float* out) {
     const spt_status s = debug_common(ctx, pcm16k, n_samples, out);
     if (s != SPT_OK) return s;
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->debug_features(pcm16k, n_samples, out);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 spt_status spt_sensevoice_debug_encode(spt_sv_ctx* ctx, const float* pcm16k, size_t n_samples,
@@ -325,12 +304,10 @@ spt_status spt_sensevoice_debug_encode(spt_sv_ctx* ctx, const float* pcm16k, siz
     if (s != SPT_OK) return s;
     spt::SvInfer ip;
     if (!infer_of(ctx, params, &ip)) return SPT_ERR_INVALID_ARG;
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->debug_encode(pcm16k, n_samples, ip, out);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 spt_status spt_sensevoice_debug_frames(spt_sv_ctx* ctx, const float* pcm16k, size_t n_samples,
@@ -340,12 +317,10 @@ spt_status spt_sensevoice_debug_frames(spt_sv_ctx* ctx, const float* pcm16k, siz
     if (!top1 || !top2) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
     spt::SvInfer ip;
     if (!infer_of(ctx, params, &ip)) return SPT_ERR_INVALID_ARG;
-    try {
+    return guarded(ctx, [&] {
         ctx->eng->debug_frames(pcm16k, n_samples, ip, ids, top1, top2);
         return SPT_OK;
-    } catch (const std::exception& e) {
-        return fail(ctx, classify(e), e.what());
-    }
+    });
 }
 
 }  // extern "C"

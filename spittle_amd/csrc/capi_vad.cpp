@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/spittle_hip.h"
+#include "capi_err.h"
 #include "common.h"
 #include "vad.h"
 
@@ -24,13 +25,7 @@ struct spt_vad {
 };
 
 namespace {
-
-void set_err(char* err, size_t errlen, const std::string& m) {
-    if (err && errlen) {
-        strncpy(err, m.c_str(), errlen - 1);
-        err[errlen - 1] = 0;
-    }
-}
+using spt::set_err;
 
 spt_status fail(spt_vad* v, spt_status s, const std::string& m) {
     if (v) v->err = m;

@@ -1,8 +1,10 @@
-// k_ms.hip -- Moonshine kernels (gfx950): the PCM stem's framing / GroupNorm / gathers, bias-free
-// LayerNorm, partial interleaved rotary, the dh <= 64 MFMA flash attention of the encoder, and the
-// decode step's GEMV / attention / argmax.  The GEMMs themselves are gemm_nt (k_gemm.hip).
+// k_ms.hip -- Moonshine kernels (gfx950): the PCM stem's framing / GroupNorm / gathers,
+// partial interleaved rotary, and the decode step's GEMV / attention / argmax.  The LayerNorm, the
+// encoder's flash attention (head tile 64) and the top-2 reduction are seq_kernels.h' text,
+// instantiated here.  The GEMMs themselves are gemm_nt (k_gemm.hip).
 #include "common.h"
 #include "ms_kernels.h"
+#include "seq_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -15,23 +17,6 @@ namespace {
 __device__ inline float gelu_erf(float x) {
 #pragma clang fp contract(off)
     return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
-}
-
-// LayerNorm / GroupNorm output of one element (contraction off, as gelu_erf)
-__device__ inline float norm_out(float v, float mean, float rstd, float g, float b) {
-#pragma clang fp contract(off)
-    return (v - mean) * rstd * g + b;
-}
-
-__device__ inline float block_sum(float v, float* red) {  // blockDim.x a multiple of 64, <= 1024
-    v = wave_sum(v);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[w] = v;
-    __syncthreads();
-    float s = 0.0f;
-    for (int i = 0; i < nw; i++) s += red[i];  // the same order in every thread
-    return s;
 }
 
 __global__ void frames_kernel(const float* pcm, int64_t stride, const int* lens, int T1p, float* frames) {
@@ -79,7 +64,7 @@ __global__ void gather2_kernel(const float* h, const float* stats, const float* 
         const int k = o / dp, c = o % dp;
         float v = 0.0f;
         if (t2 < T2 && c < d)  // 3 t2 + k <= 3 (T2 - 1) + 6 < T1
-            v = norm_out(h[((int64_t)b * T1p + t2 * MS_S2 + k) * dp + c], mean, rstd, gw[c], gb[c]);
+            v = ln_out(h[((int64_t)b * T1p + t2 * MS_S2 + k) * dp + c], mean, rstd, gw[c], gb[c]);
         row[o] = (f16)v;
     }
 }
@@ -106,25 +91,6 @@ __global__ void gelu_rows_kernel(float* x, const int* lens, int li, int Tp, int 
 __global__ void gelu_f16_kernel(const float* x, int64_t n, f16* y) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         y[i] = (f16)gelu_erf(x[i]);
-}
-
-// one wave per row
-template <typename OutT>
-__global__ void layernorm_kernel(const float* x, int M, int d, int ldx, const float* w, OutT* y, int ldy) {
-    const int m = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (m >= M) return;
-    const float* xr = x + (int64_t)m * ldx;
-    float s = 0.0f;
-    for (int c = lane; c < d; c += 64) s += xr[c];
-    const float mean = wave_sum(s) / (float)d;
-    float q = 0.0f;
-    for (int c = lane; c < d; c += 64) {
-        const float v = xr[c] - mean;
-        q += v * v;
-    }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + 1e-5f);
-    OutT* yr = y + (int64_t)m * ldy;
-    for (int c = lane; c < ldy; c += 64) yr[c] = c < d ? (OutT)norm_out(xr[c], mean, rstd, w[c], 0.0f) : (OutT)0.0f;
 }
 
 // the pair (x[2i], x[2i+1]) of a head's first `rot` dims rotated by the angle of (pos, i)
@@ -168,121 +134,6 @@ __global__ void rope_dec_kernel(const float* qkv32, int R, int H, int dh, int ro
         dst[at + 1] = (f16)c;
     }
     for (int c = threadIdx.x; c < d; c += blockDim.x) vdst[c] = (f16)src[2 * d + c];
-}
-
-// ---------------------------------------------------------------- encoder attention (MFMA, dh <= 64)
-// Workgroup = 4 waves = 64 queries of one (b, h); 64-key tiles of K (row-major) and V (transposed)
-// staged in LDS with the head dim zero-padded to 64 and keys >= T3_b stored as zero; a masked key's
-// probability is set to 0 (not multiplied to 0), so nothing a masked key holds reaches the output.
-// v_mfma_f32_16x16x32_f16: A[row l&15][k = 8 (l>>4) + j], B[k = 8 (l>>4) + j][col l&15],
-// C[row 4 (l>>4) + reg][col l&15].
-constexpr int ATT_LD = 72;  // LDS row pitch (f16): 64 + 8, rows stay 16-byte aligned
-
-__global__ void __launch_bounds__(256) enc_attn_kernel(MsAttnArgs a, float scale) {
-    __shared__ __attribute__((aligned(16))) f16 Ks[64 * ATT_LD];
-    __shared__ __attribute__((aligned(16))) f16 Vt[64 * ATT_LD];
-    __shared__ __attribute__((aligned(16))) f16 Ps[4 * 16 * ATT_LD];
-    const int b = blockIdx.z, h = blockIdx.y, q0 = blockIdx.x * 64;
-    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, lr = l & 15, lg = l >> 4;
-    const int nk = a.lens[b * 4 + 3], dh = a.dh;
-    const f16* qb = (const f16*)a.q + b * a.q_bstride + h * dh;
-    const f16* kb = (const f16*)a.k + b * a.k_bstride + h * dh;
-    const f16* vb = (const f16*)a.v + b * a.k_bstride + h * dh;
-    f16* ob = (f16*)a.out + b * a.o_bstride + h * dh;
-    if (q0 >= nk) {  // a padded query block: zero rows
-        for (int o = tid; o < 64 * dh; o += 256) {
-            const int q = q0 + o / dh;
-            if (q < a.Tq) ob[(int64_t)q * a.ldo + o % dh] = (f16)0.0f;
-        }
-        return;
-    }
-    f16x8 qa[2];
-    {
-        const int q = q0 + w * 16 + lr;
-        for (int ks = 0; ks < 2; ks++)
-            for (int j = 0; j < 8; j++) {
-                const int e = ks * 32 + lg * 8 + j;
-                qa[ks][j] = (q < nk && e < dh) ? qb[(int64_t)q * a.ldq + e] : (f16)0.0f;
-            }
-    }
-    f32x4 O[4];
-    float m_run[4], l_run[4];
-    for (int i = 0; i < 4; i++) {
-        O[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        m_run[i] = -INFINITY;
-        l_run[i] = 0.0f;
-    }
-    f16* Pw = Ps + w * 16 * ATT_LD;
-    for (int k0 = 0; k0 < nk; k0 += 64) {
-        __syncthreads();  // the previous tile's reads are done
-        {
-            const int key = tid >> 2, e0 = (tid & 3) * 16;
-            const bool kvalid = k0 + key < nk;
-            for (int c = 0; c < 16; c += 4) {
-                const int e = e0 + c;
-                f16 kv[4] = {(f16)0.0f, (f16)0.0f, (f16)0.0f, (f16)0.0f}, vv[4] = {(f16)0.0f, (f16)0.0f, (f16)0.0f, (f16)0.0f};
-                if (kvalid && e < dh) {  // dh % 4 == 0: a group of 4 dims is inside or outside the head
-                    const int64_t at = (int64_t)(k0 + key) * a.ldk + e;
-                    for (int j = 0; j < 4; j++) {
-                        kv[j] = kb[at + j];
-                        vv[j] = vb[at + j];
-                    }
-                }
-                for (int j = 0; j < 4; j++) {
-                    Ks[key * ATT_LD + e + j] = kv[j];
-                    Vt[(e + j) * ATT_LD + key] = vv[j];
-                }
-            }
-        }
-        __syncthreads();
-        f32x4 S[4];
-        for (int n = 0; n < 4; n++) {
-            S[n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            for (int ks = 0; ks < 2; ks++) {
-                const f16x8 kf = *(const f16x8*)&Ks[(n * 16 + lr) * ATT_LD + ks * 32 + lg * 8];
-                S[n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(qa[ks], kf, S[n], 0, 0, 0);
-            }
-        }
-        for (int r = 0; r < 4; r++) {  // query row 4 lg + r; its 64 keys: 4 tiles x the 16 lanes of this lane group
-            float mx = -INFINITY;
-            bool valid[4];
-            for (int n = 0; n < 4; n++) {
-                valid[n] = k0 + n * 16 + lr < nk;
-                S[n][r] = valid[n] ? S[n][r] * scale : -INFINITY;
-                mx = fmaxf(mx, S[n][r]);
-            }
-            for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-            const float m_new = fmaxf(m_run[r], mx);  // finite: key k0 of this tile is valid
-            const float alpha = m_run[r] == -INFINITY ? 0.0f : __expf(m_run[r] - m_new);
-            float ps = 0.0f;
-            for (int n = 0; n < 4; n++) {
-                const float p = valid[n] ? __expf(S[n][r] - m_new) : 0.0f;
-                ps += p;
-                Pw[(lg * 4 + r) * ATT_LD + n * 16 + lr] = (f16)p;
-            }
-            for (int o = 1; o < 16; o <<= 1) ps += __shfl_xor(ps, o, 64);
-            l_run[r] = l_run[r] * alpha + ps;
-            m_run[r] = m_new;
-            for (int dn = 0; dn < 4; dn++) O[dn][r] *= alpha;
-        }
-        __syncthreads();  // P visible to the whole wave
-        for (int ks = 0; ks < 2; ks++) {
-            const f16x8 pf = *(const f16x8*)&Pw[lr * ATT_LD + ks * 32 + lg * 8];
-            for (int dn = 0; dn < 4; dn++) {
-                const f16x8 vf = *(const f16x8*)&Vt[(dn * 16 + lr) * ATT_LD + ks * 32 + lg * 8];
-                O[dn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(pf, vf, O[dn], 0, 0, 0);
-            }
-        }
-    }
-    for (int r = 0; r < 4; r++) {
-        const int q = q0 + w * 16 + lg * 4 + r;
-        if (q >= a.Tq) continue;
-        const float inv = q < nk ? 1.0f / l_run[r] : 0.0f;
-        for (int dn = 0; dn < 4; dn++) {
-            const int e = dn * 16 + lr;
-            if (e < dh) ob[(int64_t)q * a.ldo + e] = (f16)(q < nk ? O[dn][r] * inv : 0.0f);
-        }
-    }
 }
 
 // ---------------------------------------------------------------- decode attention (one query per row)
@@ -398,36 +249,11 @@ __global__ void embed_kernel(const f16* emb, int d, const int* cur_tok, const in
 }
 
 __global__ void __launch_bounds__(256) finalize_kernel(MsFinArgs a) {
-    __shared__ float v1s[256], v2s[256];
-    __shared__ int i1s[256];
-    const int r = blockIdx.x, tid = threadIdx.x;
+    const int r = blockIdx.x;
     const MsState* s = a.s;
-    const float* lg = s->logits + (s->log_all ? (int64_t)s->step * a.R * a.V : 0) + (int64_t)r * a.V;
-    float v1 = -INFINITY, v2 = -INFINITY;
-    int i1 = 0x7FFFFFFF;
-    for (int i = tid; i < a.V; i += 256) {  // ascending: a tie keeps the lower index
-        const float v = lg[i];
-        if (v > v1) { v2 = v1; v1 = v; i1 = i; }
-        else if (v > v2) v2 = v;
-    }
-    v1s[tid] = v1; v2s[tid] = v2; i1s[tid] = i1;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-            const float b1 = v1s[tid + o], b2 = v2s[tid + o];
-            const int bi = i1s[tid + o];
-            if (b1 > v1s[tid] || (b1 == v1s[tid] && bi < i1s[tid])) {
-                v2s[tid] = fmaxf(v1s[tid], b2);
-                v1s[tid] = b1;
-                i1s[tid] = bi;
-            } else
-                v2s[tid] = fmaxf(v2s[tid], b1);
-        }
-        __syncthreads();
-    }
-    if (tid != 0) return;
-    int tok = i1s[0];
-    if (tok < 0 || tok >= a.V) tok = 0;  // a row of NaNs
+    const RowTop2 t = row_top2(s->logits + (s->log_all ? (int64_t)s->step * a.R * a.V : 0) + (int64_t)r * a.V, a.V);
+    if (threadIdx.x != 0) return;
+    const int tok = t.tok;
     a.cur_tok[r] = tok;
     if (a.done[r]) return;
     if (tok == s->eos && s->forced_len == 0) {
@@ -438,8 +264,8 @@ __global__ void __launch_bounds__(256) finalize_kernel(MsFinArgs a) {
     const int n = a.n_out[r];
     if (n < s->cap) {
         a.out_tok[(int64_t)r * s->cap + n] = tok;
-        a.out_top1[(int64_t)r * s->cap + n] = v1s[0];
-        a.out_top2[(int64_t)r * s->cap + n] = v2s[0];
+        a.out_top1[(int64_t)r * s->cap + n] = t.v1;
+        a.out_top2[(int64_t)r * s->cap + n] = t.v2;
     }
     a.n_out[r] = n + 1;
     if (n + 1 >= a.limit[r]) a.done[r] = 1;
@@ -476,9 +302,7 @@ void ms_gelu_f16(const float* x, int64_t n, void* y, hipStream_t st) {
     SPT_LAUNCH_CHECK();
 }
 void ms_layernorm(const float* x, int M, int d, int ldx, const float* w, void* y, int ldy, bool out_f32, hipStream_t st) {
-    if (out_f32) layernorm_kernel<float><<<cdiv(M, 4), 256, 0, st>>>(x, M, d, ldx, w, (float*)y, ldy);
-    else layernorm_kernel<f16><<<cdiv(M, 4), 256, 0, st>>>(x, M, d, ldx, w, (f16*)y, ldy);
-    SPT_LAUNCH_CHECK();
+    layernorm_launch(x, M, d, ldx, w, nullptr, 1e-5f, y, ldy, out_f32, st);
 }
 void ms_rope_enc(const float* qkv32, int B, int Tp, int H, int dh, int rot, int dp, const float* tab, void* qkv16,
                  hipStream_t st) {
@@ -492,9 +316,12 @@ void ms_rope_dec(const float* qkv32, int R, int H, int dh, int rot, int d, const
 }
 void ms_attention(int mode, const MsAttnArgs& a, hipStream_t st) {
     if (a.dh > 64 || a.dh % 4) throw std::runtime_error("ms_attention: head dim must be a multiple of 4, <= 64");
-    const float scale = 1.0f / sqrtf((float)a.dh);
-    if (mode == MS_ATT_ENC) enc_attn_kernel<<<dim3(cdiv(a.Tq, 64), a.H, a.B), 256, 0, st>>>(a, scale);
-    else dec_attn_kernel<<<dim3(a.H, a.B), 256, DEC_ATT_MAXK * sizeof(float), st>>>(mode, a, scale);
+    if (mode == MS_ATT_ENC) {
+        flash_attn_launch<64, false>(SeqAttnArgs{a.q, a.ldq, a.q_bstride, a.k, a.v, a.ldk, a.k_bstride, a.out, a.ldo,
+                                                 a.o_bstride, a.lens, a.B, a.H, a.dh, a.Tq}, st);
+        return;
+    }
+    dec_attn_kernel<<<dim3(a.H, a.B), 256, DEC_ATT_MAXK * sizeof(float), st>>>(mode, a, 1.0f / sqrtf((float)a.dh));
     SPT_LAUNCH_CHECK();
 }
 void ms_gemv(int mode, const void* x16, int R, int K, const void* W, const float* bias, int N, void* out,

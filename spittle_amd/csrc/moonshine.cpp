@@ -13,43 +13,14 @@
 namespace spt {
 
 namespace {
-enum { T_VEC = 0, T_MAT16 = 1, T_CONV1 = 2, T_CONVK = 3, T_TIED = 4 };
+enum { T_CONV1 = 2, T_CONVK = 3, T_TIED = 4 };  // the kinds beside SeqEngine's T_VEC and T_MAT16
 inline int pad64(int v) { return (v + 63) / 64 * 64; }
-
-void gemm(int dtype, int epi, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,
-          void* C, int ldc, hipStream_t st) {
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.sA = 0;
-    g.W = W; g.ldw = ldw;
-    g.M = M; g.N = N; g.K = K;
-    g.bias = bias;
-    g.C = C; g.ldc = ldc; g.sC = 0;
-    g.alpha = 1.0f; g.ksplit = 1; g.c_split = 0; g.nmajor = 0; g.groups = 1;
-    // the automatic variant wants N % 128 == 0, so a narrower N names the 64 x 64 tile.  The rest name
-    // the 128 x 128 tile: k_gemm.hip states its 128 / 64-row tiles bitwise equal, not the 256 x 256
-    // kernel the automatic choice may take at a large M, and a batch row must get what it gets alone
-    gemm_nt_variant(dtype, epi, g, 1, N % 128 == 0 ? 1 : 5, st);
-}
 }  // namespace
-
-void MoonshineEngine::select() const { HIP_CHECK(hipSetDevice(dev_)); }
-
-void* MoonshineEngine::dalloc(int64_t bytes, bool weight) {
-    void* p = nullptr;
-    if (bytes <= 0) bytes = 16;
-    if (hipMalloc(&p, (size_t)bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        throw std::runtime_error("moonshine: out of device memory (" + std::to_string(bytes) + " bytes)");
-    }
-    allocs_.push_back(p);
-    HIP_CHECK(hipMemset(p, 0, (size_t)bytes));
-    (weight ? weight_bytes_ : work_bytes_) += bytes;
-    return p;
-}
 
 MoonshineEngine::MoonshineEngine(const MsDims& dims, int device, int max_batch, int max_samples, uint64_t seed,
                                  bool synthetic)
-    : D_(dims), dev_(device), Bm_(max_batch), Ns_(max_samples) {
+    : SeqEngine("moonshine", device, max_batch, max_samples), D_(dims) {
+    static_assert(T_CONV1 == T_ENGINE, "the engine's kinds start at T_ENGINE");
     const MsDims& D = D_;
     if (D.d != D.H * D.dh || D.dh > 64 || D.dh % 4 || D.rot % 2 || D.rot > D.dh || D.d % 32 || D.ff % 32 || D.rot < 2)
         throw std::runtime_error("moonshine: unsupported dimensions");
@@ -62,134 +33,110 @@ MoonshineEngine::MoonshineEngine(const MsDims& dims, int device, int max_batch, 
     T1m_ = frames1(Ns_); T2m_ = frames2(T1m_); T3m_ = frames3(T2m_);
     ctx_ = std::max(448, (int)ceil(6.5 * (double)Ns_ / 16000.0) + 8);
     if (T3m_ > 8192 || ctx_ > 8192) throw std::runtime_error("moonshine: max_samples too large for the decode attention");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || dev_ < 0 || dev_ >= ndev) {
-        (void)hipGetLastError();
-        throw HipError("moonshine: no HIP device " + std::to_string(dev_));
+    open(5);
+    // a throw from here on: ~SeqEngine frees what was allocated
+    gemm_prepare();
+    const int d = D.d, V = D.vocab, ff = D.ff;
+    // ---- weights
+    conv1_ = (float*)dalloc((int64_t)dp_ * MS_K1P * 4, true);
+    gn_w_ = (float*)dalloc(d * 4, true);
+    gn_b_ = (float*)dalloc(d * 4, true);
+    conv2_ = dalloc((int64_t)n2p_ * MS_K2 * dp_ * 2, true);
+    b2_ = (float*)dalloc(n2p_ * 4, true);
+    conv3_ = dalloc((int64_t)dp_ * MS_K3 * n2p_ * 2, true);
+    b3_ = (float*)dalloc(dp_ * 4, true);
+    enc_.resize(D.n_enc);
+    for (auto& L : enc_) {
+        L.ln1 = (float*)dalloc(d * 4, true);
+        L.ln2 = (float*)dalloc(d * 4, true);
+        L.qkv = dalloc((int64_t)3 * dp_ * dp_ * 2, true);
+        L.o = dalloc((int64_t)dp_ * dp_ * 2, true);
+        L.fc1 = dalloc((int64_t)ffp_ * dp_ * 2, true);
+        L.fc1b = (float*)dalloc(ffp_ * 4, true);
+        L.fc2 = dalloc((int64_t)dp_ * ffp_ * 2, true);
+        L.fc2b = (float*)dalloc(dp_ * 4, true);
     }
-    select();
-    try {
-        HIP_CHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-        ev_.resize(5);
-        for (auto& e : ev_) HIP_CHECK(hipEventCreate(&e));
-        gemm_prepare();
-        const int d = D.d, V = D.vocab, ff = D.ff;
-        // ---- weights
-        conv1_ = (float*)dalloc((int64_t)dp_ * MS_K1P * 4, true);
-        gn_w_ = (float*)dalloc(d * 4, true);
-        gn_b_ = (float*)dalloc(d * 4, true);
-        conv2_ = dalloc((int64_t)n2p_ * MS_K2 * dp_ * 2, true);
-        b2_ = (float*)dalloc(n2p_ * 4, true);
-        conv3_ = dalloc((int64_t)dp_ * MS_K3 * n2p_ * 2, true);
-        b3_ = (float*)dalloc(dp_ * 4, true);
-        enc_.resize(D.n_enc);
-        for (auto& L : enc_) {
-            L.ln1 = (float*)dalloc(d * 4, true);
-            L.ln2 = (float*)dalloc(d * 4, true);
-            L.qkv = dalloc((int64_t)3 * dp_ * dp_ * 2, true);
-            L.o = dalloc((int64_t)dp_ * dp_ * 2, true);
-            L.fc1 = dalloc((int64_t)ffp_ * dp_ * 2, true);
-            L.fc1b = (float*)dalloc(ffp_ * 4, true);
-            L.fc2 = dalloc((int64_t)dp_ * ffp_ * 2, true);
-            L.fc2b = (float*)dalloc(dp_ * 4, true);
-        }
-        enc_ln_ = (float*)dalloc(d * 4, true);
-        emb_ = dalloc((int64_t)V * d * 2, true);
-        dec_.resize(D.n_dec);
-        for (auto& L : dec_) {
-            L.ln1 = (float*)dalloc(d * 4, true);
-            L.ln2 = (float*)dalloc(d * 4, true);
-            L.ln3 = (float*)dalloc(d * 4, true);
-            L.sqkv = dalloc((int64_t)3 * d * d * 2, true);
-            L.so = dalloc((int64_t)d * d * 2, true);
-            L.cq = dalloc((int64_t)d * d * 2, true);
-            L.ckv = dalloc((int64_t)2 * dp_ * dp_ * 2, true);
-            L.co = dalloc((int64_t)d * d * 2, true);
-            L.fc1 = dalloc((int64_t)2 * ff * d * 2, true);
-            L.fc1b = (float*)dalloc(2 * ff * 4, true);
-            L.fc2 = dalloc((int64_t)d * ff * 2, true);
-            L.fc2b = (float*)dalloc(d * 4, true);
-        }
-        dec_ln_ = (float*)dalloc(d * 4, true);
-        // rotary table [P][rot] = cos | sin, as HF: inv_freq, the angle and cos / sin in f32
-        {
-            const int P = std::max(T3m_, ctx_), half = D.rot / 2;
-            std::vector<float> tab((size_t)P * D.rot);
-            for (int i = 0; i < half; i++) {
-                const float inv = 1.0f / powf(D.theta, (float)(2 * i) / (float)D.rot);
-                for (int p = 0; p < P; p++) {
-                    const float ang = inv * (float)p;
-                    tab[(size_t)p * D.rot + i] = cosf(ang);
-                    tab[(size_t)p * D.rot + half + i] = sinf(ang);
-                }
+    enc_ln_ = (float*)dalloc(d * 4, true);
+    emb_ = dalloc((int64_t)V * d * 2, true);
+    dec_.resize(D.n_dec);
+    for (auto& L : dec_) {
+        L.ln1 = (float*)dalloc(d * 4, true);
+        L.ln2 = (float*)dalloc(d * 4, true);
+        L.ln3 = (float*)dalloc(d * 4, true);
+        L.sqkv = dalloc((int64_t)3 * d * d * 2, true);
+        L.so = dalloc((int64_t)d * d * 2, true);
+        L.cq = dalloc((int64_t)d * d * 2, true);
+        L.ckv = dalloc((int64_t)2 * dp_ * dp_ * 2, true);
+        L.co = dalloc((int64_t)d * d * 2, true);
+        L.fc1 = dalloc((int64_t)2 * ff * d * 2, true);
+        L.fc1b = (float*)dalloc(2 * ff * 4, true);
+        L.fc2 = dalloc((int64_t)d * ff * 2, true);
+        L.fc2b = (float*)dalloc(d * 4, true);
+    }
+    dec_ln_ = (float*)dalloc(d * 4, true);
+    // rotary table [P][rot] = cos | sin, as HF: inv_freq, the angle and cos / sin in f32
+    {
+        const int P = std::max(T3m_, ctx_), half = D.rot / 2;
+        std::vector<float> tab((size_t)P * D.rot);
+        for (int i = 0; i < half; i++) {
+            const float inv = 1.0f / powf(D.theta, (float)(2 * i) / (float)D.rot);
+            for (int p = 0; p < P; p++) {
+                const float ang = inv * (float)p;
+                tab[(size_t)p * D.rot + i] = cosf(ang);
+                tab[(size_t)p * D.rot + half + i] = sinf(ang);
             }
-            rope_ = (float*)dalloc((int64_t)tab.size() * 4, true);
-            HIP_CHECK(hipMemcpy(rope_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         }
-        // ---- workspace (capacity: max_batch utterances of max_samples)
-        const int64_t M1 = (int64_t)Bm_ * T1m_, M2 = (int64_t)Bm_ * T2m_, M3 = (int64_t)Bm_ * T3m_;
-        pcm_ = (float*)dalloc((int64_t)Bm_ * Ns_ * 4, false);
-        frames_ = (float*)dalloc(M1 * MS_K1P * 4, false);
-        h1_ = (float*)dalloc(M1 * dp_ * 4, false);
-        stats_ = (float*)dalloc(Bm_ * 2 * 4, false);
-        A2_ = dalloc(M2 * MS_K2 * dp_ * 2, false);
-        c2_ = (float*)dalloc(M2 * n2p_ * 4, false);
-        A3_ = dalloc(M3 * MS_K3 * n2p_ * 2, false);
-        x_ = (float*)dalloc(M3 * dp_ * 4, false);
-        xn16_ = dalloc(M3 * dp_ * 2, false);
-        qkv32_ = (float*)dalloc(M3 * 3 * dp_ * 4, false);
-        qkv16_ = dalloc(M3 * 3 * dp_ * 2, false);
-        att16_ = dalloc(M3 * dp_ * 2, false);
-        h32_ = (float*)dalloc(M3 * ffp_ * 4, false);
-        h16_ = dalloc(M3 * ffp_ * 2, false);
-        enc16_ = dalloc(M3 * dp_ * 2, false);
-        enc32_ = (float*)dalloc((int64_t)T3m_ * dp_ * 4, false);
-        for (int l = 0; l < D.n_dec; l++) ckv_.push_back(dalloc(M3 * 2 * dp_ * 2, false));
-        lens_ = (int*)dalloc(Bm_ * 4 * 4, false);
-        state_ = (MsState*)dalloc(sizeof(MsState), false);
-        cur_tok_ = (int*)dalloc(Bm_ * 4, false);
-        done_ = (int*)dalloc(Bm_ * 4, false);
-        n_out_ = (int*)dalloc(Bm_ * 4, false);
-        hit_eos_ = (int*)dalloc(Bm_ * 4, false);
-        limit_ = (int*)dalloc(Bm_ * 4, false);
-        forced_ = (int*)dalloc((int64_t)Bm_ * ctx_ * 4, false);
-        out_tok_ = (int*)dalloc((int64_t)Bm_ * ctx_ * 4, false);
-        out_top1_ = (float*)dalloc((int64_t)Bm_ * ctx_ * 4, false);
-        out_top2_ = (float*)dalloc((int64_t)Bm_ * ctx_ * 4, false);
-        dx_ = (float*)dalloc((int64_t)Bm_ * d * 4, false);
-        dqkv32_ = (float*)dalloc((int64_t)Bm_ * 3 * d * 4, false);
-        logits_ = (float*)dalloc((int64_t)Bm_ * V * 4, false);
-        dxn16_ = dalloc((int64_t)Bm_ * d * 2, false);
-        dq16_ = dalloc((int64_t)Bm_ * d * 2, false);
-        datt16_ = dalloc((int64_t)Bm_ * d * 2, false);
-        dg16_ = dalloc((int64_t)Bm_ * ff * 2, false);
-        cache_ = dalloc((int64_t)D.n_dec * 2 * Bm_ * ctx_ * d * 2, false);
-        build_tensors();
-        if (synthetic) gen_synthetic(seed);
-        HIP_CHECK(hipDeviceSynchronize());
-    } catch (...) {
-        for (auto& kv : graphs_) (void)hipGraphExecDestroy(kv.second);
-        for (void* p : allocs_) (void)hipFree(p);
-        for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-        if (st_) (void)hipStreamDestroy(st_);
-        throw;
+        rope_ = (float*)dalloc((int64_t)tab.size() * 4, true);
+        HIP_CHECK(hipMemcpy(rope_, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     }
+    // ---- workspace (capacity: max_batch utterances of max_samples)
+    const int64_t M1 = (int64_t)Bm_ * T1m_, M2 = (int64_t)Bm_ * T2m_, M3 = (int64_t)Bm_ * T3m_;
+    pcm_ = (float*)dalloc((int64_t)Bm_ * Ns_ * 4, false);
+    frames_ = (float*)dalloc(M1 * MS_K1P * 4, false);
+    h1_ = (float*)dalloc(M1 * dp_ * 4, false);
+    stats_ = (float*)dalloc(Bm_ * 2 * 4, false);
+    A2_ = dalloc(M2 * MS_K2 * dp_ * 2, false);
+    c2_ = (float*)dalloc(M2 * n2p_ * 4, false);
+    A3_ = dalloc(M3 * MS_K3 * n2p_ * 2, false);
+    x_ = (float*)dalloc(M3 * dp_ * 4, false);
+    xn16_ = dalloc(M3 * dp_ * 2, false);
+    qkv32_ = (float*)dalloc(M3 * 3 * dp_ * 4, false);
+    qkv16_ = dalloc(M3 * 3 * dp_ * 2, false);
+    att16_ = dalloc(M3 * dp_ * 2, false);
+    h32_ = (float*)dalloc(M3 * ffp_ * 4, false);
+    h16_ = dalloc(M3 * ffp_ * 2, false);
+    enc16_ = dalloc(M3 * dp_ * 2, false);
+    enc32_ = (float*)dalloc((int64_t)T3m_ * dp_ * 4, false);
+    for (int l = 0; l < D.n_dec; l++) ckv_.push_back(dalloc(M3 * 2 * dp_ * 2, false));
+    lens_ = (int*)dalloc(Bm_ * 4 * 4, false);
+    state_ = (MsState*)dalloc(sizeof(MsState), false);
+    cur_tok_ = (int*)dalloc(Bm_ * 4, false);
+    done_ = (int*)dalloc(Bm_ * 4, false);
+    n_out_ = (int*)dalloc(Bm_ * 4, false);
+    hit_eos_ = (int*)dalloc(Bm_ * 4, false);
+    limit_ = (int*)dalloc(Bm_ * 4, false);
+    forced_ = (int*)dalloc((int64_t)Bm_ * ctx_ * 4, false);
+    out_tok_ = (int*)dalloc((int64_t)Bm_ * ctx_ * 4, false);
+    out_top1_ = (float*)dalloc((int64_t)Bm_ * ctx_ * 4, false);
+    out_top2_ = (float*)dalloc((int64_t)Bm_ * ctx_ * 4, false);
+    dx_ = (float*)dalloc((int64_t)Bm_ * d * 4, false);
+    dqkv32_ = (float*)dalloc((int64_t)Bm_ * 3 * d * 4, false);
+    logits_ = (float*)dalloc((int64_t)Bm_ * V * 4, false);
+    dxn16_ = dalloc((int64_t)Bm_ * d * 2, false);
+    dq16_ = dalloc((int64_t)Bm_ * d * 2, false);
+    datt16_ = dalloc((int64_t)Bm_ * d * 2, false);
+    dg16_ = dalloc((int64_t)Bm_ * ff * 2, false);
+    cache_ = dalloc((int64_t)D.n_dec * 2 * Bm_ * ctx_ * d * 2, false);
+    build_tensors();
+    if (synthetic) gen_synthetic(seed);
+    HIP_CHECK(hipDeviceSynchronize());
 }
 
-MoonshineEngine::~MoonshineEngine() {
+MoonshineEngine::~MoonshineEngine() {  // the step graphs and the debug buffer; ~SeqEngine frees the rest
     (void)hipSetDevice(dev_);
     if (st_) (void)hipStreamSynchronize(st_);
     for (auto& kv : graphs_) (void)hipGraphExecDestroy(kv.second);
     if (logits_dbg_) (void)hipFree(logits_dbg_);
-    for (void* p : allocs_) (void)hipFree(p);
-    for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-    if (st_) (void)hipStreamDestroy(st_);
-}
-
-void MoonshineEngine::add_tensor(const std::string& name, int64_t numel, int kind, void* dst, int N, int K, int ld,
-                                 int row0, int Kw) {
-    tensor_ix_[name] = (int)tensors_.size();
-    tensors_.push_back(Tensor{name, numel, kind, dst, N, K, ld, row0, Kw, false});
 }
 
 void MoonshineEngine::build_tensors() {
@@ -243,38 +190,9 @@ void MoonshineEngine::build_tensors() {
     tensors_.back().set = true;  // tied to embed_tokens: never required
 }
 
-int64_t MoonshineEngine::tensor_numel(const std::string& name) const {
-    auto it = tensor_ix_.find(name);
-    return it == tensor_ix_.end() ? -1 : tensors_[it->second].numel;
-}
-
-int MoonshineEngine::missing() const {
-    int n = 0;
-    for (const Tensor& t : tensors_) n += t.set ? 0 : 1;
-    return n;
-}
-
-void MoonshineEngine::require_weights() const {
-    for (const Tensor& t : tensors_)
-        if (!t.set) throw std::runtime_error("moonshine: tensor not set: " + t.name + " (" + std::to_string(missing()) + " missing)");
-}
-
-void MoonshineEngine::set_tensor(const std::string& name, const float* data, int64_t n) {
-    auto it = tensor_ix_.find(name);
-    if (it == tensor_ix_.end()) throw std::runtime_error("moonshine: unknown tensor '" + name + "'");
-    Tensor& t = tensors_[it->second];
-    if (!data || n != t.numel)
-        throw std::runtime_error("moonshine: tensor '" + name + "' has " + std::to_string(t.numel) + " elements, got " + std::to_string(n));
-    select();
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (t.kind == T_VEC) {
-        HIP_CHECK(hipMemcpy(t.dst, data, (size_t)n * 4, hipMemcpyHostToDevice));
-    } else if (t.kind == T_MAT16) {
-        std::vector<uint16_t> h((size_t)t.N * t.ld, 0);
-        for (int r = 0; r < t.N; r++)
-            for (int k = 0; k < t.K; k++) h[(size_t)r * t.ld + k] = f2h_bits(data[(size_t)r * t.K + k]);
-        HIP_CHECK(hipMemcpy((uint16_t*)t.dst + (size_t)t.row0 * t.ld, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    } else if (t.kind == T_CONV1) {
+void MoonshineEngine::set_special(const Tensor& t, const float* data) {
+    const int64_t n = t.numel;
+    if (t.kind == T_CONV1) {
         std::vector<float> h((size_t)t.N * MS_K1P, 0.0f);
         for (int r = 0; r < t.N; r++)
             for (int k = 0; k < MS_K1; k++) h[(size_t)r * MS_K1P + k] = data[(size_t)r * MS_K1 + k];
@@ -295,54 +213,13 @@ void MoonshineEngine::set_tensor(const std::string& name, const float* data, int
         for (int64_t i = 0; i < n; i++)
             if (h[(size_t)i] != f2h_bits(data[i])) throw std::runtime_error("moonshine: proj_out.weight is not tied to embed_tokens.weight");
     }
-    t.set = true;
-}
-
-void MoonshineEngine::gen_synthetic(uint64_t seed) {
-    int64_t maxn = 0;
-    for (const Tensor& t : tensors_) maxn = std::max(maxn, t.numel);
-    float* tmp = nullptr;
-    HIP_CHECK(hipMalloc((void**)&tmp, (size_t)maxn * 4));
-    std::vector<float> h((size_t)maxn);
-    try {
-        uint32_t tid = 0;
-        for (size_t i = 0; i < tensors_.size(); i++, tid++) {
-            const Tensor t = tensors_[i];
-            if (t.kind == T_TIED) continue;
-            const bool is_norm = t.name.find("norm.weight") != std::string::npos;
-            const bool is_bias = t.name.find(".bias") != std::string::npos;
-            gen_weights(DT_F32, tmp, t.numel, seed, tid, is_norm ? WK_LNW : is_bias ? WK_BIAS : WK_MAT,
-                        is_norm ? -3 : is_bias ? -5 : -4, st_);
-            HIP_CHECK(hipMemcpyAsync(h.data(), tmp, (size_t)t.numel * 4, hipMemcpyDeviceToHost, st_));
-            HIP_CHECK(hipStreamSynchronize(st_));
-            set_tensor(t.name, h.data(), t.numel);
-        }
-    } catch (...) {
-        (void)hipFree(tmp);
-        throw;
-    }
-    HIP_CHECK(hipFree(tmp));
 }
 
 void MoonshineEngine::upload(const float* const* pcm, const size_t* n, int B) {
-    if (B < 1 || B > Bm_) throw std::runtime_error("moonshine: batch outside 1..max_batch");
-    std::vector<int> lens((size_t)B * 4);
-    size_t nmax = 0;
-    T1p_ = T2p_ = T3p_ = 0;
-    for (int b = 0; b < B; b++) {
-        if (!pcm[b] || n[b] < (size_t)MS_MIN_SAMPLES || n[b] > (size_t)Ns_)
-            throw std::runtime_error("moonshine: utterance of " + std::to_string(n[b]) + " samples (takes " +
-                                     std::to_string(MS_MIN_SAMPLES) + ".." + std::to_string(Ns_) + ")");
-        const int t1 = frames1((int64_t)n[b]), t2 = frames2(t1), t3 = frames3(t2);
-        lens[b * 4] = (int)n[b]; lens[b * 4 + 1] = t1; lens[b * 4 + 2] = t2; lens[b * 4 + 3] = t3;
-        T1p_ = std::max(T1p_, t1); T2p_ = std::max(T2p_, t2); T3p_ = std::max(T3p_, t3);
-        nmax = std::max(nmax, n[b]);
-    }
-    stride_ = (int64_t)nmax;
-    for (int b = 0; b < B; b++)
-        HIP_CHECK(hipMemcpyAsync(pcm_ + b * stride_, pcm[b], n[b] * 4, hipMemcpyHostToDevice, st_));
-    HIP_CHECK(hipMemcpyAsync(lens_, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, st_));
-    HIP_CHECK(hipStreamSynchronize(st_));  // lens (a local) has been read
+    SeqEngine::upload(pcm, n, B, MS_MIN_SAMPLES, [](int64_t ns, int* len) {
+        len[1] = frames1(ns); len[2] = frames2(len[1]); len[3] = frames3(len[2]);
+    });
+    T1p_ = lens_max_[1]; T2p_ = lens_max_[2]; T3p_ = lens_max_[3];
 }
 
 void MoonshineEngine::run_stem(int B) {
@@ -495,8 +372,8 @@ std::vector<MsUtt> MoonshineEngine::transcribe(const float* const* pcm, const si
     HIP_CHECK(hipMemcpyAsync(t1.data(), out_top1_, t1.size() * 4, hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipMemcpyAsync(t2.data(), out_top2_, t2.size() * 4, hipMemcpyDeviceToHost, st_));
     HIP_CHECK(hipStreamSynchronize(st_));
-    float ms[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 4; i++) HIP_CHECK(hipEventElapsedTime(&ms[i], ev_[i], ev_[i + 1]));
+    float ms[4];
+    phase_ms(4, ms);
     tm_.stem_ms = ms[0]; tm_.encoder_ms = ms[1]; tm_.cross_kv_ms = ms[2]; tm_.decode_ms = ms[3];
     tm_.total_ms = (double)ms[0] + ms[1] + ms[2] + ms[3];
     tm_.n_steps = steps; tm_.batch = B;

@@ -14,6 +14,7 @@
 
 #include "ms_host.h"
 #include "ms_kernels.h"
+#include "seq_engine.h"
 
 namespace spt {
 
@@ -28,25 +29,15 @@ struct MsTimings {
     int n_steps = 0, batch = 0;
 };
 
-class MoonshineEngine {
+// The tensor names are the HF state dict's (SeqEngine::set_tensor).
+class MoonshineEngine : public SeqEngine {
 public:
     MoonshineEngine(const MsDims& dims, int device, int max_batch, int max_samples, uint64_t seed, bool synthetic);
-    ~MoonshineEngine();
-    MoonshineEngine(const MoonshineEngine&) = delete;
-    MoonshineEngine& operator=(const MoonshineEngine&) = delete;
+    ~MoonshineEngine() override;
 
     const MsDims& dims() const { return D_; }
-    int max_batch() const { return Bm_; }
-    int max_samples() const { return Ns_; }
     int ctx() const { return ctx_; }
-    int64_t weight_bytes() const { return weight_bytes_; }
-    int64_t workspace_bytes() const { return work_bytes_; }
     const MsTimings& timings() const { return tm_; }
-
-    // HF state-dict names; numel -1 for an unknown name
-    int64_t tensor_numel(const std::string& name) const;
-    void set_tensor(const std::string& name, const float* data, int64_t n);
-    int missing() const;
 
     static int frames1(int64_t n) { return n < MS_K1 ? 0 : (int)((n - MS_K1) / MS_S1 + 1); }
     static int frames2(int t1) { return t1 < MS_K2 ? 0 : (t1 - MS_K2) / MS_S2 + 1; }
@@ -63,23 +54,12 @@ public:
     void clear_timings() { tm_ = MsTimings(); }
 
 private:
-    struct Tensor {
-        std::string name;
-        int64_t numel;
-        int kind;
-        void* dst;
-        int N, K, ld, row0, Kw;
-        bool set;
-    };
     struct EncLayer { float *ln1, *ln2, *fc1b, *fc2b; void *qkv, *o, *fc1, *fc2; };
     struct DecLayer { float *ln1, *ln2, *ln3, *fc1b, *fc2b; void *sqkv, *so, *cq, *ckv, *co, *fc1, *fc2; };
 
-    void select() const;
-    void* dalloc(int64_t bytes, bool weight);
-    void add_tensor(const std::string& name, int64_t numel, int kind, void* dst, int N, int K, int ld, int row0, int Kw);
     void build_tensors();
-    void gen_synthetic(uint64_t seed);
-    void require_weights() const;
+    // conv1's padded rows, the conv2 / conv3 re-layout, and the check of the tied proj_out
+    void set_special(const Tensor& t, const float* data) override;
     void upload(const float* const* pcm, const size_t* n, int B);
     void run_stem(int B);
     void run_encoder(int B);
@@ -89,15 +69,8 @@ private:
     int run_decode(int R, const int* limit, const int* forced, int forced_len, float* logits_all);
 
     MsDims D_;
-    int dev_, Bm_, Ns_, dp_, n2_, n2p_, ffp_, ctx_, T1m_, T2m_, T3m_;
-    int T1p_ = 0, T2p_ = 0, T3p_ = 0;
-    int64_t stride_ = 0;
-    hipStream_t st_ = nullptr;
-    std::vector<hipEvent_t> ev_;
-    std::vector<void*> allocs_;
-    int64_t weight_bytes_ = 0, work_bytes_ = 0;
-    std::vector<Tensor> tensors_;
-    std::map<std::string, int> tensor_ix_;
+    int dp_, n2_, n2p_, ffp_, ctx_, T1m_, T2m_, T3m_;
+    int T1p_ = 0, T2p_ = 0, T3p_ = 0;  // this call's padded frame counts
     MsTimings tm_;
     // weights
     float *conv1_, *gn_w_, *gn_b_, *b2_, *b3_, *enc_ln_, *dec_ln_, *rope_;
@@ -105,10 +78,9 @@ private:
     std::vector<EncLayer> enc_;
     std::vector<DecLayer> dec_;
     // workspace
-    float *pcm_, *frames_, *h1_, *stats_, *c2_, *x_, *qkv32_, *h32_, *enc32_;
+    float *frames_, *h1_, *stats_, *c2_, *x_, *qkv32_, *h32_, *enc32_;
     void *A2_, *A3_, *xn16_, *qkv16_, *att16_, *h16_, *enc16_;
     std::vector<void*> ckv_;
-    int* lens_;
     // decode
     MsState* state_;
     int *cur_tok_, *done_, *n_out_, *hit_eos_, *limit_, *forced_, *out_tok_;

@@ -26,10 +26,12 @@
 #include <thread>
 #include <vector>
 
+#include "capi_err.h"
 #include "capi_internal.h"
 #include "common.h"
 
 namespace {
+using spt::set_err;
 
 struct Rccl {
     void* h = nullptr;
@@ -59,13 +61,6 @@ const Rccl& rccl() {
         return x;
     }();
     return r;
-}
-
-void set_err(char* buf, size_t len, const std::string& msg) {
-    if (buf && len) {
-        strncpy(buf, msg.c_str(), len - 1);
-        buf[len - 1] = 0;
-    }
 }
 
 // contiguous balanced shard [begin, end) of n items for rank r of w (spittle_amd.dist.shard_range)

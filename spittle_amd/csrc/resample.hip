@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/spittle_hip.h"
+#include "capi_err.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -111,13 +112,7 @@ struct spt_resampler {
 };
 
 namespace {
-
-void set_err(char* err, size_t errlen, const std::string& m) {
-    if (err && errlen) {
-        strncpy(err, m.c_str(), errlen - 1);
-        err[errlen - 1] = 0;
-    }
-}
+using spt::set_err;
 
 // rubato FftFixedIn filter (oracle/resampler.py filter_taps): Blackman-Harris^2-windowed sinc,
 // fft_size_in taps centred at nin / 2, unit sum, divided by 2 nin; its spectrum over 2 nin points

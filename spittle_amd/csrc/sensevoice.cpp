@@ -13,42 +13,12 @@
 namespace spt {
 
 namespace {
-enum { T_VEC = 0, T_MAT16 = 1 };
 constexpr int SV_CTC_CHUNK = 2048;  // rows per CTC GEMM (bounds the f32 logits buffer)
-
-void gemm(int dtype, int epi, const void* A, int lda, const void* W, int ldw, int M, int N, int K, const float* bias,
-          void* C, int ldc, hipStream_t st) {
-    GemmArgs g{};
-    g.A = A; g.lda = lda; g.sA = 0;
-    g.W = W; g.ldw = ldw;
-    g.M = M; g.N = N; g.K = K;
-    g.bias = bias;
-    g.C = C; g.ldc = ldc; g.sC = 0;
-    g.alpha = 1.0f; g.ksplit = 1; g.c_split = 0; g.nmajor = 0; g.groups = 1;
-    // named tiles, never the automatic choice: the 128 x 128 and 64 x 64 tiles are bitwise equal and do
-    // not depend on M, so a batch row gets what it gets alone (as the Moonshine engine)
-    gemm_nt_variant(dtype, epi, g, 1, N % 128 == 0 ? 1 : 5, st);
-}
 }  // namespace
-
-void SenseVoiceEngine::select() const { HIP_CHECK(hipSetDevice(dev_)); }
-
-void* SenseVoiceEngine::dalloc(int64_t bytes, bool weight) {
-    void* p = nullptr;
-    if (bytes <= 0) bytes = 16;
-    if (hipMalloc(&p, (size_t)bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        throw std::runtime_error("sensevoice: out of device memory (" + std::to_string(bytes) + " bytes)");
-    }
-    allocs_.push_back(p);
-    HIP_CHECK(hipMemset(p, 0, (size_t)bytes));
-    (weight ? weight_bytes_ : work_bytes_) += bytes;
-    return p;
-}
 
 SenseVoiceEngine::SenseVoiceEngine(const SvDims& dims, int device, int max_batch, int max_samples, uint64_t seed,
                                    bool synthetic)
-    : D_(dims), dev_(device), Bm_(max_batch), Ns_(max_samples) {
+    : SeqEngine("sensevoice", device, max_batch, max_samples), D_(dims) {
     const SvDims& D = D_;
     std::string derr;
     if (!sv_dims_ok(D, &derr)) throw std::runtime_error(derr);
@@ -59,91 +29,74 @@ SenseVoiceEngine::SenseVoiceEngine(const SvDims& dims, int device, int max_batch
     Vp_ = (D.vocab + 127) / 128 * 128;
     Tm_ = sv_frames_of(Ns_);
     Rm_ = sv_rows_of(Ns_, D.lfr_n);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || dev_ < 0 || dev_ >= ndev) {
-        (void)hipGetLastError();
-        throw HipError("sensevoice: no HIP device " + std::to_string(dev_));
+    open(4);
+    // a throw from here on: ~SeqEngine frees what was allocated
+    gemm_prepare();
+    const int d = D.d, ff = D.ff;
+    // ---- tables and weights
+    win_ = (float*)dalloc(SV_FRAME * 4, true);
+    basis_ = (float*)dalloc((int64_t)SV_DFT_N * SV_NFFT * 4, true);
+    fbT_ = (float*)dalloc((int64_t)SV_NBIN * SV_MELS * 4, true);
+    inv_freq_ = (float*)dalloc((int64_t)(in_ / 2) * 4, true);
+    neg_mean_ = (float*)dalloc(in_ * 4, true);
+    inv_std_ = (float*)dalloc(in_ * 4, true);
+    embed_ = (float*)dalloc((int64_t)SV_EMBED_ROWS * in_ * 4, true);
+    layers_.resize(D.layers());
+    for (int l = 0; l < D.layers(); l++) {
+        Layer& L = layers_[l];
+        L.din = l < D.n0 ? in_ : d;
+        L.ldin = l < D.n0 ? inp_ : d;
+        L.n1w = (float*)dalloc(L.din * 4, true);
+        L.n1b = (float*)dalloc(L.din * 4, true);
+        L.qkv = dalloc((int64_t)3 * d * L.ldin * 2, true);
+        L.qkvb = (float*)dalloc(3 * d * 4, true);
+        L.fsmn = (float*)dalloc((int64_t)d * SV_FSMN_K * 4, true);
+        L.o = dalloc((int64_t)d * d * 2, true);
+        L.ob = (float*)dalloc(d * 4, true);
+        L.n2w = (float*)dalloc(d * 4, true);
+        L.n2b = (float*)dalloc(d * 4, true);
+        L.w1 = dalloc((int64_t)ff * d * 2, true);
+        L.w1b = (float*)dalloc(ff * 4, true);
+        L.w2 = dalloc((int64_t)d * ff * 2, true);
+        L.w2b = (float*)dalloc(d * 4, true);
     }
-    select();
-    try {
-        HIP_CHECK(hipStreamCreateWithFlags(&st_, hipStreamNonBlocking));
-        ev_.resize(4);
-        for (auto& e : ev_) HIP_CHECK(hipEventCreate(&e));
-        gemm_prepare();
-        const int d = D.d, ff = D.ff;
-        // ---- tables and weights
-        win_ = (float*)dalloc(SV_FRAME * 4, true);
-        basis_ = (float*)dalloc((int64_t)SV_DFT_N * SV_NFFT * 4, true);
-        fbT_ = (float*)dalloc((int64_t)SV_NBIN * SV_MELS * 4, true);
-        inv_freq_ = (float*)dalloc((int64_t)(in_ / 2) * 4, true);
-        neg_mean_ = (float*)dalloc(in_ * 4, true);
-        inv_std_ = (float*)dalloc(in_ * 4, true);
-        embed_ = (float*)dalloc((int64_t)SV_EMBED_ROWS * in_ * 4, true);
-        layers_.resize(D.layers());
-        for (int l = 0; l < D.layers(); l++) {
-            Layer& L = layers_[l];
-            L.din = l < D.n0 ? in_ : d;
-            L.ldin = l < D.n0 ? inp_ : d;
-            L.n1w = (float*)dalloc(L.din * 4, true);
-            L.n1b = (float*)dalloc(L.din * 4, true);
-            L.qkv = dalloc((int64_t)3 * d * L.ldin * 2, true);
-            L.qkvb = (float*)dalloc(3 * d * 4, true);
-            L.fsmn = (float*)dalloc((int64_t)d * SV_FSMN_K * 4, true);
-            L.o = dalloc((int64_t)d * d * 2, true);
-            L.ob = (float*)dalloc(d * 4, true);
-            L.n2w = (float*)dalloc(d * 4, true);
-            L.n2b = (float*)dalloc(d * 4, true);
-            L.w1 = dalloc((int64_t)ff * d * 2, true);
-            L.w1b = (float*)dalloc(ff * 4, true);
-            L.w2 = dalloc((int64_t)d * ff * 2, true);
-            L.w2b = (float*)dalloc(d * 4, true);
-        }
-        an_w_ = (float*)dalloc(d * 4, true);
-        an_b_ = (float*)dalloc(d * 4, true);
-        tn_w_ = (float*)dalloc(d * 4, true);
-        tn_b_ = (float*)dalloc(d * 4, true);
-        ctc_w_ = dalloc((int64_t)Vp_ * d * 2, true);   // pad rows stay zero
-        ctc_b_ = (float*)dalloc(Vp_ * 4, true);
-        // ---- workspace (capacity: max_batch utterances of max_samples)
-        const int64_t MT = (int64_t)Bm_ * Tm_, MR = (int64_t)Bm_ * Rm_;
-        if (MT * SV_DFT_N >= (1ll << 31) || MR * std::max(3 * d, std::max(ff, inp_)) >= (1ll << 31))
-            throw std::runtime_error("sensevoice: max_batch x max_samples too large");
-        chunk_ = (int)std::min<int64_t>(MR, SV_CTC_CHUNK);
-        pcm_ = (float*)dalloc((int64_t)Bm_ * Ns_ * 4, false);
-        frames_ = (float*)dalloc(MT * SV_NFFT * 4, false);
-        spec_ = (float*)dalloc(MT * SV_DFT_N * 4, false);
-        mel_ = (float*)dalloc(MT * SV_MELS * 4, false);
-        rows_ = (float*)dalloc(MR * inp_ * 4, false);
-        x_ = (float*)dalloc(MR * d * 4, false);
-        enc32_ = (float*)dalloc((int64_t)Rm_ * d * 4, false);
-        xn16_ = dalloc(MR * std::max(inp_, d) * 2, false);
-        qkv16_ = dalloc(MR * 3 * d * 2, false);
-        att16_ = dalloc(MR * d * 2, false);
-        h16_ = dalloc(MR * ff * 2, false);
-        logits_ = (float*)dalloc((int64_t)chunk_ * Vp_ * 4, false);
-        ids_ = (int*)dalloc(MR * 4, false);
-        top1_ = (float*)dalloc(MR * 4, false);
-        top2_ = (float*)dalloc(MR * 4, false);
-        out_ = (int*)dalloc((int64_t)Bm_ * (8 + 4 * (int64_t)Rm_) * 4, false);
-        lens_ = (int*)dalloc(Bm_ * 4 * 4, false);
-        upload_tables();
-        build_tensors();
-        if (synthetic) gen_synthetic(seed);
-        HIP_CHECK(hipDeviceSynchronize());
-    } catch (...) {
-        for (void* p : allocs_) (void)hipFree(p);
-        for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-        if (st_) (void)hipStreamDestroy(st_);
-        throw;
+    an_w_ = (float*)dalloc(d * 4, true);
+    an_b_ = (float*)dalloc(d * 4, true);
+    tn_w_ = (float*)dalloc(d * 4, true);
+    tn_b_ = (float*)dalloc(d * 4, true);
+    ctc_w_ = dalloc((int64_t)Vp_ * d * 2, true);   // pad rows stay zero
+    ctc_b_ = (float*)dalloc(Vp_ * 4, true);
+    // ---- workspace (capacity: max_batch utterances of max_samples)
+    const int64_t MT = (int64_t)Bm_ * Tm_, MR = (int64_t)Bm_ * Rm_;
+    if (MT * SV_DFT_N >= (1ll << 31) || MR * std::max(3 * d, std::max(ff, inp_)) >= (1ll << 31))
+        throw std::runtime_error("sensevoice: max_batch x max_samples too large");
+    chunk_ = (int)std::min<int64_t>(MR, SV_CTC_CHUNK);
+    pcm_ = (float*)dalloc((int64_t)Bm_ * Ns_ * 4, false);
+    frames_ = (float*)dalloc(MT * SV_NFFT * 4, false);
+    spec_ = (float*)dalloc(MT * SV_DFT_N * 4, false);
+    mel_ = (float*)dalloc(MT * SV_MELS * 4, false);
+    rows_ = (float*)dalloc(MR * inp_ * 4, false);
+    x_ = (float*)dalloc(MR * d * 4, false);
+    enc32_ = (float*)dalloc((int64_t)Rm_ * d * 4, false);
+    xn16_ = dalloc(MR * std::max(inp_, d) * 2, false);
+    qkv16_ = dalloc(MR * 3 * d * 2, false);
+    att16_ = dalloc(MR * d * 2, false);
+    h16_ = dalloc(MR * ff * 2, false);
+    logits_ = (float*)dalloc((int64_t)chunk_ * Vp_ * 4, false);
+    ids_ = (int*)dalloc(MR * 4, false);
+    top1_ = (float*)dalloc(MR * 4, false);
+    top2_ = (float*)dalloc(MR * 4, false);
+    out_ = (int*)dalloc((int64_t)Bm_ * (8 + 4 * (int64_t)Rm_) * 4, false);
+    lens_ = (int*)dalloc(Bm_ * 4 * 4, false);
+    upload_tables();
+    build_tensors();
+    if (synthetic) {
+        gen_synthetic(seed);
+        // a log-mel of speech-level PCM x 32768 sits near 10 with a spread of a few units
+        std::vector<float> nm((size_t)in_, -10.0f), is((size_t)in_, 0.25f);
+        set_cmvn(nm.data(), is.data(), in_);
     }
-}
-
-SenseVoiceEngine::~SenseVoiceEngine() {
-    (void)hipSetDevice(dev_);
-    if (st_) (void)hipStreamSynchronize(st_);
-    for (void* p : allocs_) (void)hipFree(p);
-    for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
-    if (st_) (void)hipStreamDestroy(st_);
+    HIP_CHECK(hipDeviceSynchronize());
 }
 
 void SenseVoiceEngine::upload_tables() {
@@ -175,11 +128,6 @@ void SenseVoiceEngine::upload_tables() {
     HIP_CHECK(hipMemcpy(basis_, basis.data(), basis.size() * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(fbT_, fbT.data(), fbT.size() * 4, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(inv_freq_, inv.data(), inv.size() * 4, hipMemcpyHostToDevice));
-}
-
-void SenseVoiceEngine::add_tensor(const std::string& name, int64_t numel, int kind, void* dst, int N, int K, int ld) {
-    tensor_ix_[name] = (int)tensors_.size();
-    tensors_.push_back(Tensor{name, numel, kind, dst, N, K, ld, false});
 }
 
 void SenseVoiceEngine::build_tensors() {
@@ -216,40 +164,13 @@ void SenseVoiceEngine::build_tensors() {
     if (!same) throw std::runtime_error("sensevoice: tensor table out of step with sv_tensor_names");
 }
 
-int64_t SenseVoiceEngine::tensor_numel(const std::string& name) const {
-    auto it = tensor_ix_.find(name);
-    return it == tensor_ix_.end() ? -1 : tensors_[it->second].numel;
-}
-
 int SenseVoiceEngine::missing() const {
-    int n = cmvn_set_ ? 0 : 1;
-    for (const Tensor& t : tensors_) n += t.set ? 0 : 1;
-    return n;
+    return SeqEngine::missing() + (cmvn_set_ ? 0 : 1);
 }
 
 void SenseVoiceEngine::require_weights() const {
-    for (const Tensor& t : tensors_)
-        if (!t.set) throw std::runtime_error("sensevoice: tensor not set: " + t.name + " (" + std::to_string(missing()) + " missing)");
+    SeqEngine::require_weights();
     if (!cmvn_set_) throw std::runtime_error("sensevoice: CMVN not set");
-}
-
-void SenseVoiceEngine::set_tensor(const std::string& name, const float* data, int64_t n) {
-    auto it = tensor_ix_.find(name);
-    if (it == tensor_ix_.end()) throw std::runtime_error("sensevoice: unknown tensor '" + name + "'");
-    Tensor& t = tensors_[it->second];
-    if (!data || n != t.numel)
-        throw std::runtime_error("sensevoice: tensor '" + name + "' has " + std::to_string(t.numel) + " elements, got " + std::to_string(n));
-    select();
-    HIP_CHECK(hipStreamSynchronize(st_));
-    if (t.kind == T_VEC) {
-        HIP_CHECK(hipMemcpy(t.dst, data, (size_t)n * 4, hipMemcpyHostToDevice));
-    } else {
-        std::vector<uint16_t> h((size_t)t.N * t.ld, 0);
-        for (int r = 0; r < t.N; r++)
-            for (int k = 0; k < t.K; k++) h[(size_t)r * t.ld + k] = f2h_bits(data[(size_t)r * t.K + k]);
-        HIP_CHECK(hipMemcpy(t.dst, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    }
-    t.set = true;
 }
 
 void SenseVoiceEngine::set_cmvn(const float* neg_mean, const float* inv_std, int n) {
@@ -262,53 +183,12 @@ void SenseVoiceEngine::set_cmvn(const float* neg_mean, const float* inv_std, int
     cmvn_set_ = true;
 }
 
-void SenseVoiceEngine::gen_synthetic(uint64_t seed) {
-    int64_t maxn = 0;
-    for (const Tensor& t : tensors_) maxn = std::max(maxn, t.numel);
-    float* tmp = nullptr;
-    HIP_CHECK(hipMalloc((void**)&tmp, (size_t)maxn * 4));
-    std::vector<float> h((size_t)maxn);
-    try {
-        uint32_t tid = 0;
-        for (size_t i = 0; i < tensors_.size(); i++, tid++) {
-            const Tensor t = tensors_[i];
-            const bool is_bias = t.name.find(".bias") != std::string::npos;
-            const bool is_norm = !is_bias && t.name.find("norm") != std::string::npos;
-            gen_weights(DT_F32, tmp, t.numel, seed, tid, is_norm ? WK_LNW : is_bias ? WK_BIAS : WK_MAT,
-                        is_norm ? -3 : is_bias ? -5 : -4, st_);
-            HIP_CHECK(hipMemcpyAsync(h.data(), tmp, (size_t)t.numel * 4, hipMemcpyDeviceToHost, st_));
-            HIP_CHECK(hipStreamSynchronize(st_));
-            set_tensor(t.name, h.data(), t.numel);
-        }
-    } catch (...) {
-        (void)hipFree(tmp);
-        throw;
-    }
-    HIP_CHECK(hipFree(tmp));
-    // a log-mel of speech-level PCM x 32768 sits near 10 with a spread of a few units
-    std::vector<float> nm((size_t)in_, -10.0f), is((size_t)in_, 0.25f);
-    set_cmvn(nm.data(), is.data(), in_);
-}
-
 void SenseVoiceEngine::upload(const float* const* pcm, const size_t* n, int B) {
-    if (B < 1 || B > Bm_) throw std::runtime_error("sensevoice: batch outside 1..max_batch");
-    std::vector<int> lens((size_t)B * 4);
-    size_t nmax = 0;
-    Tp_ = Rp_ = 0;
-    for (int b = 0; b < B; b++) {
-        if (!pcm[b] || n[b] < (size_t)SV_FRAME || n[b] > (size_t)Ns_)
-            throw std::runtime_error("sensevoice: utterance of " + std::to_string(n[b]) + " samples (takes " +
-                                     std::to_string(SV_FRAME) + ".." + std::to_string(Ns_) + ")");
-        const int T = sv_frames_of((int64_t)n[b]), Tl = sv_lfr_rows_of(T, D_.lfr_n);
-        lens[b * 4] = (int)n[b]; lens[b * 4 + 1] = T; lens[b * 4 + 2] = Tl; lens[b * 4 + 3] = Tl + SV_NQ;
-        Tp_ = std::max(Tp_, T); Rp_ = std::max(Rp_, Tl + SV_NQ);
-        nmax = std::max(nmax, n[b]);
-    }
-    stride_ = (int64_t)nmax;
-    for (int b = 0; b < B; b++)
-        HIP_CHECK(hipMemcpyAsync(pcm_ + b * stride_, pcm[b], n[b] * 4, hipMemcpyHostToDevice, st_));
-    HIP_CHECK(hipMemcpyAsync(lens_, lens.data(), lens.size() * 4, hipMemcpyHostToDevice, st_));
-    HIP_CHECK(hipStreamSynchronize(st_));  // lens (a local) has been read
+    const int lfr_n = D_.lfr_n;
+    SeqEngine::upload(pcm, n, B, SV_FRAME, [lfr_n](int64_t ns, int* len) {
+        len[1] = sv_frames_of(ns); len[2] = sv_lfr_rows_of(len[1], lfr_n); len[3] = len[2] + SV_NQ;
+    });
+    Tp_ = lens_max_[1]; Rp_ = lens_max_[3];
 }
 
 void SenseVoiceEngine::run_frontend(int B, const SvInfer& p, bool feat_only) {
@@ -381,8 +261,8 @@ std::vector<SvUtt> SenseVoiceEngine::transcribe(const float* const* pcm, const s
     std::vector<int> out((size_t)(B * stride));
     HIP_CHECK(hipMemcpyAsync(out.data(), out_, out.size() * 4, hipMemcpyDeviceToHost, st_));  // the one read-back
     HIP_CHECK(hipStreamSynchronize(st_));
-    float ms[3] = {0, 0, 0};
-    for (int i = 0; i < 3; i++) HIP_CHECK(hipEventElapsedTime(&ms[i], ev_[i], ev_[i + 1]));
+    float ms[3];
+    phase_ms(3, ms);
     tm_.frontend_ms = ms[0]; tm_.encoder_ms = ms[1]; tm_.ctc_ms = ms[2];
     tm_.total_ms = (double)ms[0] + ms[1] + ms[2];
     tm_.rows = Rp_; tm_.batch = B;

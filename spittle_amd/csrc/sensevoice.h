@@ -7,11 +7,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "seq_engine.h"
 #include "sv_host.h"
 #include "sv_kernels.h"
 
@@ -33,29 +33,20 @@ struct SvInfer {
     bool use_itn = false;
 };
 
-class SenseVoiceEngine {
+// The tensor names are the FunASR state dict's (SeqEngine::set_tensor).
+class SenseVoiceEngine : public SeqEngine {
 public:
     SenseVoiceEngine(const SvDims& dims, int device, int max_batch, int max_samples, uint64_t seed, bool synthetic);
-    ~SenseVoiceEngine();
-    SenseVoiceEngine(const SenseVoiceEngine&) = delete;
-    SenseVoiceEngine& operator=(const SenseVoiceEngine&) = delete;
 
     const SvDims& dims() const { return D_; }
-    int max_batch() const { return Bm_; }
-    int max_samples() const { return Ns_; }
     int max_rows() const { return Rm_; }
-    int64_t weight_bytes() const { return weight_bytes_; }
-    int64_t workspace_bytes() const { return work_bytes_; }
     const SvTimings& timings() const { return tm_; }
     void clear_timings() { tm_ = SvTimings(); }
 
-    // FunASR state-dict names; numel -1 for an unknown name
-    int64_t tensor_numel(const std::string& name) const;
-    void set_tensor(const std::string& name, const float* data, int64_t n);
     // (x + neg_mean) * inv_std over the LFR width
     void set_cmvn(const float* neg_mean, const float* inv_std, int n);
     // tensors (and the CMVN pair, counted as one) still to be supplied
-    int missing() const;
+    int missing() const override;
 
     int rows_of(int64_t n) const { return sv_rows_of(n, D_.lfr_n); }
 
@@ -69,27 +60,15 @@ public:
     void debug_frames(const float* pcm, size_t n, const SvInfer& p, int* ids, float* top1, float* top2);
 
 private:
-    struct Tensor {
-        std::string name;
-        int64_t numel;
-        int kind;
-        void* dst;
-        int N, K, ld;
-        bool set;
-    };
     struct Layer {
         int din, ldin;
         float *n1w, *n1b, *qkvb, *fsmn, *ob, *n2w, *n2b, *w1b, *w2b;
         void *qkv, *o, *w1, *w2;
     };
 
-    void select() const;
-    void* dalloc(int64_t bytes, bool weight);
-    void add_tensor(const std::string& name, int64_t numel, int kind, void* dst, int N, int K, int ld);
     void build_tensors();
     void upload_tables();
-    void gen_synthetic(uint64_t seed);
-    void require_weights() const;
+    void require_weights() const override;
     void upload(const float* const* pcm, const size_t* n, int B);
     void run_frontend(int B, const SvInfer& p, bool feat_only);
     void norm16(const float* x, int M, int d, int ld, const float* w, const float* b, void* y);
@@ -97,15 +76,8 @@ private:
     void run_ctc(int B);
 
     SvDims D_;
-    int dev_, Bm_, Ns_, in_, inp_, Vp_, Tm_, Rm_, chunk_;
-    int Tp_ = 0, Rp_ = 0;
-    int64_t stride_ = 0;
-    hipStream_t st_ = nullptr;
-    std::vector<hipEvent_t> ev_;
-    std::vector<void*> allocs_;
-    int64_t weight_bytes_ = 0, work_bytes_ = 0;
-    std::vector<Tensor> tensors_;
-    std::map<std::string, int> tensor_ix_;
+    int in_, inp_, Vp_, Tm_, Rm_, chunk_;
+    int Tp_ = 0, Rp_ = 0;  // this call's padded fbank frames and encoder rows
     bool cmvn_set_ = false;
     SvTimings tm_;
     // tables and weights
@@ -114,9 +86,9 @@ private:
     void* ctc_w_;
     std::vector<Layer> layers_;
     // workspace
-    float *pcm_, *frames_, *spec_, *mel_, *rows_, *x_, *enc32_, *logits_, *top1_, *top2_;
+    float *frames_, *spec_, *mel_, *rows_, *x_, *enc32_, *logits_, *top1_, *top2_;
     void *xn16_, *qkv16_, *att16_, *h16_;
-    int *lens_, *ids_, *out_;
+    int *ids_, *out_;
 };
 
 }  // namespace spt
