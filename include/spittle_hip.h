@@ -391,6 +391,91 @@ spt_status spt_debug_xq_fused(int32_t device, int32_t dtype, const float* x, con
                               int32_t B, int32_t H, int32_t T_enc, int32_t lds, int32_t touch, float* q, float* out,
                               char* err, size_t errlen);
 
+/* DTW token and word timestamps from the alignment heads' cross-attention (additive over ABI 14,
+ * announced by SPT_HAS_TOKEN_TIMESTAMPS): whisper.cpp's dtw_token_timestamps, OpenAI's
+ * word_timestamps, HF's return_token_timestamps.  After each window's decoder is chosen, one
+ * teacher-forced replay of [sot, (lang, task,) <|notimestamps|>, text tokens] collects the alignment
+ * heads' attention probabilities; normalisation, a width-7 median, the head mean and a dynamic time
+ * warping (HF transformers' recurrence and tie rule) then give every text token a start and an end. */
+#define SPT_HAS_TOKEN_TIMESTAMPS 1
+typedef struct spt_token_time {
+    int64_t t0, t1;   /* 10 ms units, as spt_segment */
+    float p;          /* the token's probability */
+    int32_t index;    /* into spt_result.tokens */
+} spt_token_time;
+typedef struct spt_word {
+    int64_t t0, t1;   /* its first token's start, its last token's end */
+    char* text;       /* the tokens' bytes */
+    int32_t i0, n_tokens;  /* its tokens in spt_alignment.tokens */
+    float p;          /* mean of the token probabilities */
+} spt_word;
+typedef struct spt_alignment {
+    spt_token_time* tokens;  /* one per text token (timestamp and eot tokens have none) */
+    int32_t n_tokens;
+    spt_word* words;         /* ggml models; a synthetic model has no vocabulary and no words */
+    int32_t n_words;
+} spt_alignment;
+/* The alignment heads as n_pairs (layer, head) pairs; n_pairs = 0 restores the default, every head of
+ * the top half of the decoder layers.  A pair out of range, a duplicate or more than 512 pairs:
+ * SPT_ERR_INVALID_ARG (the heads in use stay). */
+spt_status spt_set_alignment_heads(spt_ctx* ctx, const int32_t* layer_head, int32_t n_pairs);
+/* spt_transcribe on the whisper_full path (whatever the parameters), plus the alignment of each
+ * utterance; *out is what whisper_full gives without the alignment.  Free with spt_result_free and
+ * spt_alignment_free.  The test hooks stay allowed here: forced_tokens [batch][n_forced] fixes the token
+ * fed after step s of every window of utterance u to forced_tokens[u][s] (the token recorded, and so
+ * aligned, is still the sampler's choice at that step; not with beam_size > 1), and SPT_IGNORE_EOT keeps
+ * the pass loop from ending early.  With SPT_NO_WINDOW_SHARE set the call is SPT_ERR_INVALID_ARG. */
+spt_status spt_transcribe_aligned(spt_ctx* ctx, const float* pcm16k, size_t n_samples, const spt_infer_params* params,
+                                  spt_result** out, spt_alignment** align);
+spt_status spt_transcribe_aligned_batch(spt_ctx* ctx, const float* const* pcm, const size_t* n_samples, size_t batch,
+                                        const spt_infer_params* params, spt_result** out, spt_alignment** align);
+void spt_alignment_free(spt_alignment* a);
+/* Test hook: what the last aligned call recorded: the replay passes of its last Engine::align, the
+ * alignment heads in use, and the bytes of the alignment workspace the context holds.  Any pointer may be NULL. */
+spt_status spt_debug_align_stats(spt_ctx* ctx, int32_t* replay_passes, int32_t* n_heads, int64_t* workspace_bytes);
+/* Test hook: the last aligned window of the context: the alignment heads' probabilities p
+ * [n_heads][n_rows][n_keys] (rows: each text token, then the end), the matrix m [n_rows][n_keys] and
+ * the path [path_len][2] of (row, key).  Any buffer may be NULL; the capacities are in elements. */
+spt_status spt_debug_align_last(spt_ctx* ctx, int32_t* n_heads, int32_t* n_rows, int32_t* n_keys, float* p, size_t p_cap,
+                                float* m, size_t m_cap, int32_t* path, size_t path_cap, int32_t* path_len);
+
+/* The token-alignment kernels alone (additive over ABI 14, announced by SPT_HAS_ALIGN_KERNELS;
+ * DESIGN.md 2d / 4.5): align_qk, align_norm and align_dtw of k_align.hip on caller-supplied host
+ * arrays, on a stream of their own on `device`, under the rules of the attention hooks above.  N [B]
+ * and M [B] are each sequence's text rows and keys in use (0..N_cap, 0..M_cap); what a kernel does not
+ * write comes back as NaN (ints: -1).
+ * align_qk: q [B*Tq][H*64] (rounded to dtype) are the rows pos0 .. pos0 + Tq - 1 of each sequence,
+ * k [B_layout][H][T_enc][64] (rounded to dtype) is laid out as one layer of the cross K/V cache, the V
+ * halves and the keys from T_enc to the next multiple of 32 holding pad_value; sequence b attends to
+ * window kvrow[b] (NULL: b); heads [n_heads] is any list of heads.  p [B][n_heads][N_cap][M_cap]:
+ * p[b][i][pos0 + t][s < M[b]] = softmax over all T_enc keys of q . k / 8 for head heads[i].
+ * T_enc <= 3072, M_cap <= T_enc, Tq 1..4, pos0 + Tq <= N_cap. */
+#define SPT_HAS_ALIGN_KERNELS 1
+spt_status spt_debug_align_qk(int32_t device, int32_t dtype, const float* q, const float* k, float pad_value, int32_t B,
+                              int32_t B_layout, int32_t H, int32_t T_enc, int32_t Tq, int32_t pos0,
+                              const int32_t* kvrow, const int32_t* heads, int32_t n_heads, const int32_t* M,
+                              int32_t N_cap, int32_t M_cap, float* p, char* err, size_t errlen);
+/* align_norm: p [B][A][N_cap][M_cap] -> stat [B][A][2][M_cap] (optional: each column's mean and
+ * population std over the N rows) and m [B][N_cap][M_cap] = the mean over the heads of the width-7
+ * median along the keys (reflect padding; none for M <= 3) of (p - mean) / std, 0 where std == 0. */
+spt_status spt_debug_align_norm(int32_t device, const float* p, int32_t B, int32_t A, int32_t N_cap, int32_t M_cap,
+                                const int32_t* N, const int32_t* M, float* stat, float* m, char* err, size_t errlen);
+/* align_dtw: dynamic time warping of -m (m [B][N_cap][M_cap]; N_cap <= 256, M_cap a multiple of 8, the
+ * 2-bit trace within 160 KiB) -> jump [B][N_cap] (the first key of each row on the path), len [B] and,
+ * optionally, path [B][N_cap + M_cap][2] = the (row, key) pairs in order, -1 past len. */
+spt_status spt_debug_align_dtw(int32_t device, const float* m, int32_t B, int32_t N_cap, int32_t M_cap, const int32_t* N,
+                               const int32_t* M, int32_t* jump, int32_t* len, int32_t* path, char* err,
+                               size_t errlen);
+/* Host only: n aligned tokens (piece bytes with their lengths, start t0, end t1, probability p or
+ * NULL) grouped into words: a word starts at the first token and at every token whose piece begins
+ * with a space, but a token whose bytes stop inside a UTF-8 sequence joins the next token.  Arrays of
+ * n entries receive each word's first token, token count, t0 of its first and t1 of its last token,
+ * and (word_p optional) the mean probability; *n_words the count. */
+spt_status spt_debug_align_words(const char* const* pieces, const int32_t* piece_len, const int64_t* t0,
+                                 const int64_t* t1, const float* p, int32_t n, int32_t* word_i0, int32_t* word_n,
+                                 int64_t* word_t0, int64_t* word_t1, float* word_p, int32_t* n_words, char* err,
+                                 size_t errlen);
+
 /* Quantised decoder weights resident in HBM (additive over ABI 14, announced by
  * SPT_HAS_QUANT_RESIDENT).  spt_debug_qgemv is the decoder GEMV alone over one
  * quantised matrix, with no context and no model, on a stream of its own on `device`: the launch

@@ -435,6 +435,112 @@ extern "C" {
         err: *mut c_char,
         errlen: usize,
     ) -> spt_status;
+    // DTW token and word timestamps (SPT_HAS_TOKEN_TIMESTAMPS, additive over ABI 14)
+    pub fn spt_set_alignment_heads(ctx: *mut spt_ctx, layer_head: *const i32, n_pairs: i32) -> spt_status;
+    pub fn spt_transcribe_aligned(
+        ctx: *mut spt_ctx,
+        pcm16k: *const f32,
+        n_samples: usize,
+        params: *const spt_infer_params,
+        out: *mut *mut spt_result,
+        align: *mut *mut spt_alignment,
+    ) -> spt_status;
+    pub fn spt_transcribe_aligned_batch(
+        ctx: *mut spt_ctx,
+        pcm: *const *const f32,
+        n_samples: *const usize,
+        batch: usize,
+        params: *const spt_infer_params,
+        out: *mut *mut spt_result,
+        align: *mut *mut spt_alignment,
+    ) -> spt_status;
+    pub fn spt_alignment_free(a: *mut spt_alignment);
+    pub fn spt_debug_align_stats(
+        ctx: *mut spt_ctx,
+        replay_passes: *mut i32,
+        n_heads: *mut i32,
+        workspace_bytes: *mut i64,
+    ) -> spt_status;
+    pub fn spt_debug_align_last(
+        ctx: *mut spt_ctx,
+        n_heads: *mut i32,
+        n_rows: *mut i32,
+        n_keys: *mut i32,
+        p: *mut f32,
+        p_cap: usize,
+        m: *mut f32,
+        m_cap: usize,
+        path: *mut i32,
+        path_cap: usize,
+        path_len: *mut i32,
+    ) -> spt_status;
+    // the token-alignment kernels alone (SPT_HAS_ALIGN_KERNELS, additive over ABI 14)
+    pub fn spt_debug_align_qk(
+        device: i32,
+        dtype: i32,
+        q: *const f32,
+        k: *const f32,
+        pad_value: f32,
+        b: i32,
+        b_layout: i32,
+        h: i32,
+        t_enc: i32,
+        tq: i32,
+        pos0: i32,
+        kvrow: *const i32,
+        heads: *const i32,
+        n_heads: i32,
+        m: *const i32,
+        n_cap: i32,
+        m_cap: i32,
+        p: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_align_norm(
+        device: i32,
+        p: *const f32,
+        b: i32,
+        a: i32,
+        n_cap: i32,
+        m_cap: i32,
+        n: *const i32,
+        m: *const i32,
+        stat: *mut f32,
+        m_out: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_align_dtw(
+        device: i32,
+        m: *const f32,
+        b: i32,
+        n_cap: i32,
+        m_cap: i32,
+        n: *const i32,
+        m_len: *const i32,
+        jump: *mut i32,
+        len: *mut i32,
+        path: *mut i32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_align_words(
+        pieces: *const *const c_char,
+        piece_len: *const i32,
+        t0: *const i64,
+        t1: *const i64,
+        p: *const f32,
+        n: i32,
+        word_i0: *mut i32,
+        word_n: *mut i32,
+        word_t0: *mut i64,
+        word_t1: *mut i64,
+        word_p: *mut f32,
+        n_words: *mut i32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
     pub fn spt_get_weight_residency(
         ctx: *const spt_ctx,
         resident_weights: *mut i64,
@@ -719,6 +825,40 @@ extern "C" {
 // ---- SenseVoice types
 /// The header's feature macro: the spt_sensevoice_* entry points exist.
 pub const SPT_HAS_SENSEVOICE: c_int = 1;
+/// the token-alignment kernels' test hooks (`spt_debug_align_*`) are present
+pub const SPT_HAS_ALIGN_KERNELS: c_int = 1;
+/// DTW token and word timestamps (`spt_transcribe_aligned`) are present
+pub const SPT_HAS_TOKEN_TIMESTAMPS: c_int = 1;
+
+/// a text token's start and end (10 ms units), probability and index into `spt_result.tokens`
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct spt_token_time {
+    pub t0: i64,
+    pub t1: i64,
+    pub p: f32,
+    pub index: i32,
+}
+
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct spt_word {
+    pub t0: i64,
+    pub t1: i64,
+    pub text: *mut c_char,
+    pub i0: i32,
+    pub n_tokens: i32,
+    pub p: f32,
+}
+
+#[repr(C)]
+#[derive(Debug)]
+pub struct spt_alignment {
+    pub tokens: *mut spt_token_time,
+    pub n_tokens: i32,
+    pub words: *mut spt_word,
+    pub n_words: i32,
+}
 pub const SPT_SV_LANG_AUTO: i32 = 0;
 pub const SPT_SV_LANG_ZH: i32 = 1;
 pub const SPT_SV_LANG_EN: i32 = 2;

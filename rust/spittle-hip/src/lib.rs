@@ -127,6 +127,71 @@ unsafe fn take_result(r: *mut sys::spt_result) -> TranscriptionResult {
     TranscriptionResult { text, segments: Some(segments) }
 }
 
+/// A text token's time from the alignment heads' cross-attention (`SPT_HAS_TOKEN_TIMESTAMPS`).
+#[derive(Debug, Clone, PartialEq)]
+pub struct TokenTime {
+    /// seconds, as `TranscriptionSegment`
+    pub start: f32,
+    pub end: f32,
+    /// the token's probability
+    pub probability: f32,
+    /// its index among the call's result tokens
+    pub index: usize,
+}
+
+/// A word: text tokens joined at leading spaces (a split UTF-8 character kept whole).
+#[derive(Debug, Clone, PartialEq)]
+pub struct WordTime {
+    pub start: f32,
+    pub end: f32,
+    pub text: String,
+    /// mean of its tokens' probabilities
+    pub probability: f32,
+    /// its tokens: `tokens[first_token .. first_token + n_tokens]` of the `AlignedTranscription`
+    pub first_token: usize,
+    pub n_tokens: usize,
+}
+
+/// `transcribe_samples_aligned`'s result: what `transcribe_samples` returns on the whisper_full path,
+/// plus a time for every text token and (ggml models) every word.
+pub struct AlignedTranscription {
+    pub result: TranscriptionResult,
+    pub tokens: Vec<TokenTime>,
+    pub words: Vec<WordTime>,
+}
+
+/// Copy a library-owned alignment into owned values and release it.
+///
+/// SAFETY: `a` must be an alignment returned by the library and not yet freed.
+unsafe fn take_alignment(a: *mut sys::spt_alignment) -> (Vec<TokenTime>, Vec<WordTime>) {
+    let al = &*a;
+    let tokens = (0..al.n_tokens.max(0) as usize)
+        .map(|i| {
+            let t = &*al.tokens.add(i);
+            TokenTime { start: t.t0 as f32 / 100.0, end: t.t1 as f32 / 100.0, probability: t.p, index: t.index.max(0) as usize }
+        })
+        .collect();
+    let words = if al.words.is_null() {
+        Vec::new()
+    } else {
+        (0..al.n_words.max(0) as usize)
+            .map(|i| {
+                let w = &*al.words.add(i);
+                WordTime {
+                    start: w.t0 as f32 / 100.0,
+                    end: w.t1 as f32 / 100.0,
+                    text: if w.text.is_null() { String::new() } else { CStr::from_ptr(w.text).to_string_lossy().into_owned() },
+                    probability: w.p,
+                    first_token: w.i0.max(0) as usize,
+                    n_tokens: w.n_tokens.max(0) as usize,
+                }
+            })
+            .collect()
+    };
+    sys::spt_alignment_free(a);
+    (tokens, words)
+}
+
 /// One Whisper model on one MI355X.
 pub struct HipWhisperEngine {
     ctx: *mut sys::spt_ctx,
@@ -224,6 +289,69 @@ impl HipWhisperEngine {
         }
         // SAFETY: on success every out[i] is a live library result
         Ok(out.into_iter().map(|r| unsafe { take_result(r) }).collect())
+    }
+
+    /// The alignment heads as (layer, head) pairs; an empty slice restores the default, every head of
+    /// the top half of the decoder layers (`spt_set_alignment_heads`).
+    pub fn set_alignment_heads(&mut self, pairs: &[(i32, i32)]) -> Result<(), Box<dyn Error>> {
+        self.need()?;
+        let flat: Vec<i32> = pairs.iter().flat_map(|&(l, h)| vec![l, h]).collect();
+        // SAFETY: a live context and 2 * pairs.len() readable values
+        let st = unsafe { sys::spt_set_alignment_heads(self.ctx, flat.as_ptr(), pairs.len() as i32) };
+        if st != sys::SPT_OK {
+            return Err(status_error("alignment heads", st, self.last_error()));
+        }
+        Ok(())
+    }
+
+    /// `transcribe_samples` on the whisper_full path with DTW token and word timestamps (whisper.cpp's
+    /// `dtw_token_timestamps`): one extra teacher-forced replay of each window's kept decoder.
+    pub fn transcribe_samples_aligned(
+        &mut self,
+        samples: Vec<f32>,
+        params: Option<WhisperInferenceParams>,
+    ) -> Result<AlignedTranscription, Box<dyn Error>> {
+        let mut v = self.transcribe_batch_aligned(&[samples], params)?;
+        v.pop().ok_or_else(|| "no result".into())
+    }
+
+    /// Several utterances in one aligned call.
+    pub fn transcribe_batch_aligned(
+        &mut self,
+        batch: &[Vec<f32>],
+        params: Option<WhisperInferenceParams>,
+    ) -> Result<Vec<AlignedTranscription>, Box<dyn Error>> {
+        self.need()?;
+        let rq = request(params)?;
+        let ptrs: Vec<*const f32> = batch.iter().map(|a| a.as_ptr()).collect();
+        let lens: Vec<usize> = batch.iter().map(|a| a.len()).collect();
+        let mut out = vec![std::ptr::null_mut::<sys::spt_result>(); batch.len()];
+        let mut al = vec![std::ptr::null_mut::<sys::spt_alignment>(); batch.len()];
+        // SAFETY: every pointer is valid for its length for the duration of the call
+        let st = unsafe {
+            sys::spt_transcribe_aligned_batch(
+                self.ctx,
+                ptrs.as_ptr(),
+                lens.as_ptr(),
+                batch.len(),
+                &rq.ip,
+                out.as_mut_ptr(),
+                al.as_mut_ptr(),
+            )
+        };
+        if st != sys::SPT_OK {
+            return Err(status_error("aligned transcription", st, self.last_error()));
+        }
+        // SAFETY: on success every out[i] and al[i] is live and owned by us until taken (and freed) here
+        Ok(out
+            .into_iter()
+            .zip(al)
+            .map(|(r, a)| unsafe {
+                let result = take_result(r);
+                let (tokens, words) = take_alignment(a);
+                AlignedTranscription { result, tokens, words }
+            })
+            .collect())
     }
 }
 

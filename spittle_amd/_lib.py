@@ -63,7 +63,27 @@ EXPORTS = [
     "spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross", "spt_debug_xq_fused",
     # quantised decoder weights resident in HBM (SPT_HAS_QUANT_RESIDENT)
     "spt_debug_qgemv", "spt_get_weight_residency",
+    # the token-alignment kernels alone (SPT_HAS_ALIGN_KERNELS)
+    "spt_debug_align_qk", "spt_debug_align_norm", "spt_debug_align_dtw", "spt_debug_align_words",
+    # DTW token and word timestamps (SPT_HAS_TOKEN_TIMESTAMPS)
+    "spt_set_alignment_heads", "spt_transcribe_aligned", "spt_transcribe_aligned_batch", "spt_alignment_free",
+    "spt_debug_align_last", "spt_debug_align_stats",
 ]
+
+
+class TokenTime(C.Structure):
+    _fields_ = [("t0", C.c_int64), ("t1", C.c_int64), ("p", C.c_float), ("index", C.c_int32)]
+
+
+class Word(C.Structure):
+    _fields_ = [("t0", C.c_int64), ("t1", C.c_int64), ("text", C.c_char_p), ("i0", C.c_int32), ("n_tokens", C.c_int32),
+                ("p", C.c_float)]
+
+
+class Alignment(C.Structure):
+    _fields_ = [("tokens", C.POINTER(TokenTime)), ("n_tokens", C.c_int32), ("words", C.POINTER(Word)),
+                ("n_words", C.c_int32)]
+
 SPT_MODEL_QUANT_RESIDENT = 2
 SPT_GGML_Q4_1, SPT_GGML_Q5_0, SPT_GGML_Q5_1 = 3, 6, 7
 SPT_GV_BIAS, SPT_GV_BIAS_GELU, SPT_GV_PARTIAL, SPT_GV_QKV_CACHE, SPT_GV_LOGITS, SPT_GV_BIAS_RESID = range(6)
@@ -437,6 +457,30 @@ def load():
     L.spt_debug_qgemv.restype = C.c_int
     L.spt_get_weight_residency.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.spt_get_weight_residency.restype = C.c_int
+    # the token-alignment kernels alone
+    i64p = C.POINTER(C.c_int64)
+    L.spt_debug_align_qk.argtypes = [i32, i32, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32p, i32p, i32, i32p,
+                                     i32, i32, fp, C.c_char_p, C.c_size_t]
+    L.spt_debug_align_norm.argtypes = [i32, fp, i32, i32, i32, i32, i32p, i32p, fp, fp, C.c_char_p, C.c_size_t]
+    L.spt_debug_align_dtw.argtypes = [i32, fp, i32, i32, i32, i32p, i32p, i32p, i32p, i32p, C.c_char_p, C.c_size_t]
+    L.spt_debug_align_words.argtypes = [C.POINTER(C.c_char_p), i32p, i64p, i64p, fp, i32, i32p, i32p, i64p, i64p, fp,
+                                        i32p, C.c_char_p, C.c_size_t]
+    for fn in ("spt_debug_align_qk", "spt_debug_align_norm", "spt_debug_align_dtw", "spt_debug_align_words"):
+        getattr(L, fn).restype = C.c_int
+    # DTW token and word timestamps
+    alp = C.POINTER(Alignment)
+    L.spt_set_alignment_heads.argtypes = [vp, i32p, i32]
+    L.spt_transcribe_aligned.argtypes = [vp, fp, C.c_size_t, C.POINTER(InferParams), C.POINTER(C.POINTER(Result)),
+                                         C.POINTER(alp)]
+    L.spt_transcribe_aligned_batch.argtypes = [vp, C.POINTER(fp), C.POINTER(C.c_size_t), C.c_size_t,
+                                               C.POINTER(InferParams), C.POINTER(C.POINTER(Result)), C.POINTER(alp)]
+    L.spt_alignment_free.argtypes = [alp]
+    L.spt_alignment_free.restype = None
+    L.spt_debug_align_last.argtypes = [vp, i32p, i32p, i32p, fp, C.c_size_t, fp, C.c_size_t, i32p, C.c_size_t, i32p]
+    L.spt_debug_align_stats.argtypes = [vp, i32p, i32p, C.POINTER(C.c_int64)]
+    for fn in ("spt_set_alignment_heads", "spt_transcribe_aligned", "spt_transcribe_aligned_batch", "spt_debug_align_last",
+               "spt_debug_align_stats"):
+        getattr(L, fn).restype = C.c_int
     for fn in EXPORTS:
         if fn.startswith("spt_parakeet_") and fn not in ("spt_parakeet_default_model_params",
                                                           "spt_parakeet_default_infer_params", "spt_parakeet_destroy",

@@ -9,6 +9,7 @@
 // (SPT_IGNORE_EOT, forced tokens) cut an utterance into fixed 30 s windows of its whole
 // log-mel (frames 3000 k ..), independent batch items whose text is concatenated.
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <string.h>
 
 #include <algorithm>
@@ -19,6 +20,7 @@
 
 #include "../../include/spittle_hip.h"
 #include "common.h"
+#include "align_host.h"
 #include "engine.h"
 #include "full.h"
 #include "ggml_file.h"
@@ -204,14 +206,59 @@ spt_result* make_full_result(const spt::FullResult& f, const spt::Specials& sp) 
     return r;
 }
 
-// whisper_full (full.cpp) over host utterances
+// the alignment of one utterance's result: a time for every text token, and (with a vocabulary) words
+spt_alignment* make_alignment(const spt_ctx* c, const spt::FullResult& f) {
+    spt_alignment* a = (spt_alignment*)calloc(1, sizeof(spt_alignment));
+    if (!a) return nullptr;
+    std::vector<int> idx;
+    for (size_t i = 0; i < f.tok_t0.size(); ++i)
+        if (f.tok_t0[i] >= 0) idx.push_back((int)i);
+    const size_t n = idx.size();
+    a->tokens = (spt_token_time*)calloc(n ? n : 1, sizeof(spt_token_time));
+    if (!a->tokens) { spt_alignment_free(a); return nullptr; }
+    a->n_tokens = (int32_t)n;
+    std::vector<std::string> pieces(n);
+    std::vector<int64_t> t0(n), t1(n);
+    std::vector<float> pr(n);
+    for (size_t i = 0; i < n; ++i) {
+        const int k = idx[i];
+        t0[i] = f.tok_t0[k]; t1[i] = f.tok_t1[k]; pr[i] = expf(f.plog[k]);
+        a->tokens[i] = spt_token_time{t0[i], t1[i], pr[i], k};
+        if (c->vocab) pieces[i] = c->vocab->str(f.tokens[k]);
+    }
+    if (!c->vocab || n == 0) return a;  // a synthetic model has no pieces: token times only
+    const std::vector<spt::AlignWord> w = spt::align_words(pieces, t0.data(), t1.data(), pr.data());
+    a->words = (spt_word*)calloc(w.size() ? w.size() : 1, sizeof(spt_word));
+    if (!a->words) { spt_alignment_free(a); return nullptr; }
+    a->n_words = (int32_t)w.size();
+    for (size_t i = 0; i < w.size(); ++i) {
+        spt_word& o = a->words[i];
+        o.t0 = w[i].t0; o.t1 = w[i].t1; o.i0 = w[i].i0; o.n_tokens = w[i].n; o.p = w[i].p;
+        o.text = (char*)malloc(w[i].text.size() + 1);
+        if (!o.text) { spt_alignment_free(a); return nullptr; }
+        memcpy(o.text, w[i].text.c_str(), w[i].text.size() + 1);
+    }
+    return a;
+}
+
+// whisper_full (full.cpp) over host utterances; align (optional): DTW token timestamps too
 spt_status run_full(spt_ctx* c, const float* const* pcm, const size_t* n_samples, size_t batch,
-                    const spt_infer_params* p, spt_result** out) {
+                    const spt_infer_params* p, spt_result** out, spt_alignment** align = nullptr) {
     if (p->beam_size > 8) return fail(c, SPT_ERR_INVALID_ARG, "beam_size must be at most 8");
     if (p->beam_size > c->eng->max_batch())
         return fail(c, SPT_ERR_INVALID_ARG, "beam_size exceeds the context's max_batch (one row per beam)");
-    if (p->forced_tokens || (p->flags & SPT_IGNORE_EOT))
+    const bool hooks = (p->forced_tokens && p->n_forced > 0) || (p->flags & SPT_IGNORE_EOT);
+    if (hooks && !align)
         return fail(c, SPT_ERR_INVALID_ARG, "forced tokens / SPT_IGNORE_EOT are fast-path (no-timestamp) hooks");
+    if (align) {  // the aligned call keeps both hooks (tests fix the fed text with them)
+        if (p->forced_tokens && (p->n_forced < 0 || p->n_forced > c->eng->dims().n_text_ctx))
+            return fail(c, SPT_ERR_INVALID_ARG, "n_forced out of range");
+        if (p->forced_tokens && p->n_forced > 0 && p->beam_size > 1)
+            return fail(c, SPT_ERR_INVALID_ARG, "forced tokens cannot steer a beam search");
+        const char* ns = getenv("SPT_NO_WINDOW_SHARE");
+        if (ns && atoi(ns) != 0)
+            return fail(c, SPT_ERR_INVALID_ARG, "token timestamps need the shared windows: unset SPT_NO_WINDOW_SHARE");
+    }
     if ((p->flags & SPT_SUPPRESS_NST) && !c->vocab)
         return fail(c, SPT_ERR_UNSUPPORTED, "suppressing non-speech tokens needs the vocabulary of a ggml model");
     if (p->temperature < 0.0f || p->temperature_inc < 0.0f) return fail(c, SPT_ERR_INVALID_ARG, "negative temperature");
@@ -235,6 +282,12 @@ spt_status run_full(spt_ctx* c, const float* const* pcm, const size_t* n_samples
     fp.max_initial_ts = p->max_initial_ts;
     fp.max_tokens = std::max(0, p->max_new_tokens);
     fp.seed = p->seed;
+    fp.token_timestamps = align != nullptr;
+    if (align && p->forced_tokens && p->n_forced > 0) {
+        fp.forced = p->forced_tokens;
+        fp.n_forced = p->n_forced;
+    }
+    fp.ignore_eot = align && (p->flags & SPT_IGNORE_EOT) != 0;
     std::vector<const float*> ptr(batch);
     std::vector<int> ns(batch);
     for (size_t u = 0; u < batch; ++u) {
@@ -248,8 +301,13 @@ spt_status run_full(spt_ctx* c, const float* const* pcm, const size_t* n_samples
                             lang_tok >= 0 ? lang_tok : -1, &res);
     for (size_t u = 0; u < batch; ++u) {
         out[u] = make_full_result(res[u], sp);
-        if (!out[u]) {
-            for (size_t v = 0; v < u; ++v) { spt_result_free(out[v]); out[v] = nullptr; }
+        if (align) align[u] = out[u] ? make_alignment(c, res[u]) : nullptr;
+        if (!out[u] || (align && !align[u])) {
+            for (size_t v = 0; v <= u; ++v) {
+                spt_result_free(out[v]);
+                out[v] = nullptr;
+                if (align) { spt_alignment_free(align[v]); align[v] = nullptr; }
+            }
             return fail(c, SPT_ERR_OOM, "host allocation failed");
         }
     }
@@ -737,6 +795,94 @@ spt_status spt_debug_ggml_dequant(int32_t ggml_type, const void* src, int64_t n,
     if (!blck) return SPT_ERR_UNSUPPORTED;
     if (n % blck) return SPT_ERR_INVALID_ARG;
     return spt::ggml_dequant_host(ggml_type, (const uint8_t*)src, n, dst) ? SPT_OK : SPT_ERR_UNSUPPORTED;
+}
+
+}  // extern "C"
+
+extern "C" {
+
+spt_status spt_set_alignment_heads(spt_ctx* ctx, const int32_t* layer_head, int32_t n_pairs) {
+    if (!ctx || n_pairs < 0 || (n_pairs > 0 && !layer_head)) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
+    try {
+        std::vector<std::pair<int, int>> hs;
+        for (int i = 0; i < n_pairs; ++i) hs.push_back({layer_head[2 * i], layer_head[2 * i + 1]});
+        ctx->eng->set_alignment_heads(hs);
+        return SPT_OK;
+    } catch (const std::invalid_argument& e) {
+        return fail(ctx, SPT_ERR_INVALID_ARG, e.what());
+    } catch (const std::exception& e) {
+        return fail(ctx, classify(e), e.what());
+    }
+}
+
+spt_status spt_transcribe_aligned_batch(spt_ctx* ctx, const float* const* pcm, const size_t* n_samples, size_t batch,
+                                        const spt_infer_params* params, spt_result** out, spt_alignment** align) {
+    if (!ctx || !out || !align || (batch && (!pcm || !n_samples))) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
+    spt_infer_params dflt;
+    spt_default_infer_params(&dflt);
+    if (!params) params = &dflt;
+    ctx->eng->reset_call_stats();
+    for (size_t u = 0; u < batch; ++u) {
+        out[u] = nullptr;
+        align[u] = nullptr;
+        if (n_samples[u] && !pcm[u]) return fail(ctx, SPT_ERR_INVALID_ARG, "null pcm");
+    }
+    try {
+        return batch ? run_full(ctx, pcm, n_samples, batch, params, out, align) : SPT_OK;
+    } catch (const std::exception& e) {
+        for (size_t u = 0; u < batch; ++u) {
+            spt_result_free(out[u]); out[u] = nullptr;
+            spt_alignment_free(align[u]); align[u] = nullptr;
+        }
+        return fail(ctx, classify(e), e.what());
+    }
+}
+
+spt_status spt_transcribe_aligned(spt_ctx* ctx, const float* pcm16k, size_t n_samples, const spt_infer_params* params,
+                                  spt_result** out, spt_alignment** align) {
+    if (!ctx || !out || !align) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
+    if (n_samples && !pcm16k) return fail(ctx, SPT_ERR_INVALID_ARG, "null pcm");
+    const float* p = pcm16k;
+    return spt_transcribe_aligned_batch(ctx, &p, &n_samples, 1, params, out, align);
+}
+
+void spt_alignment_free(spt_alignment* a) {
+    if (!a) return;
+    if (a->words)
+        for (int32_t i = 0; i < a->n_words; ++i) free(a->words[i].text);
+    free(a->words);
+    free(a->tokens);
+    free(a);
+}
+
+spt_status spt_debug_align_stats(spt_ctx* ctx, int32_t* replay_passes, int32_t* n_heads, int64_t* workspace_bytes) {
+    if (!ctx) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
+    if (replay_passes) *replay_passes = ctx->eng->align_passes();
+    if (n_heads) *n_heads = ctx->eng->alignment_heads();
+    if (workspace_bytes) *workspace_bytes = ctx->eng->align_workspace_bytes();
+    return SPT_OK;
+}
+
+spt_status spt_debug_align_last(spt_ctx* ctx, int32_t* n_heads, int32_t* n_rows, int32_t* n_keys, float* p, size_t p_cap,
+                                float* m, size_t m_cap, int32_t* path, size_t path_cap, int32_t* path_len) {
+    if (!ctx || !n_heads || !n_rows || !n_keys) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
+    try {
+        int A = 0, N = 0, M = 0;
+        std::vector<float> hp, hm;
+        std::vector<int> hpath;
+        if (!ctx->eng->align_last(&A, &N, &M, p ? &hp : nullptr, m ? &hm : nullptr, path ? &hpath : nullptr))
+            return fail(ctx, SPT_ERR_INVALID_ARG, "no window has been aligned on this context");
+        *n_heads = A; *n_rows = N; *n_keys = M;
+        if (path_len) *path_len = (int32_t)(hpath.size() / 2);
+        if ((p && hp.size() > p_cap) || (m && hm.size() > m_cap) || (path && hpath.size() > path_cap))
+            return fail(ctx, SPT_ERR_INVALID_ARG, "buffer too small for the last alignment");
+        if (p) memcpy(p, hp.data(), hp.size() * sizeof(float));
+        if (m) memcpy(m, hm.data(), hm.size() * sizeof(float));
+        if (path) memcpy(path, hpath.data(), hpath.size() * sizeof(int32_t));
+        return SPT_OK;
+    } catch (const std::exception& e) {
+        return fail(ctx, classify(e), e.what());
+    }
 }
 
 }  // extern "C"

@@ -179,6 +179,11 @@ void Engine::release() {
     upcm_ = umel_ = nullptr;
     uinfo_ = nullptr;
     upcm_cap_ = umel_cap_ = 0;
+    for (void* p : {(void*)al_p_, (void*)al_stat_, (void*)al_m_, (void*)al_int_, (void*)al_heads_dev_})
+        if (p) (void)hipFree(p);
+    al_p_ = al_stat_ = al_m_ = nullptr;
+    al_int_ = al_heads_dev_ = nullptr;
+    al_p_cap_ = al_stat_cap_ = al_m_cap_ = al_int_cap_ = 0;
     uinfo_cap_ = 0;
     for (void* p : {(void*)hann_, (void*)sinv_, (void*)cosv_, (void*)filt_, (void*)grp_})
         if (p) (void)hipFree(p);
@@ -1081,6 +1086,15 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
             gemv(dt_, GV_BIAS, A_LN, a, st);
         }
         consumed();
+        if (tap_ && !fuse && align_cnt_[l] > 0) {  // align(): this layer's alignment heads on the pass's q rows
+            AlignQkArgs q{};
+            q.q = g.dq; q.Tq = Tq; q.pos0 = tap_->row0;
+            q.kv = (const char*)ckv_ + cross_layer * l * esz_; q.B_layout = E; q.H = H; q.T_enc = T;
+            q.kvrow = g.kvrow;
+            q.heads = al_heads_dev_ + align_off_[l]; q.n_heads = align_cnt_[l]; q.a0 = align_off_[l];
+            q.p = tap_->p; q.A = tap_->A; q.N_cap = tap_->N_cap; q.M_cap = tap_->M_cap; q.M = tap_->M;
+            align_qk(dt_, q, B, st);
+        }
         pmark(0, l, 0);
         if (fuse) {  // the attention ran in the cross-Q launch
         } else if (vw) {
@@ -1511,6 +1525,188 @@ void Engine::decode(int B, const DecodeRequest& rq, int* tokens, float* top1, fl
     cs_.engine_calls++;
     cs_.decoder_passes += tm_.n_decode_passes;
     finish_call_timing();
+}
+
+// ----------------------------------------------------------------------------- token alignment
+void Engine::set_alignment_heads(const std::vector<std::pair<int, int>>& pairs) {
+    std::vector<std::pair<int, int>> hs = pairs;
+    if (hs.empty())  // every head of the top half of the decoder layers
+        for (int l = dm_.n_dec / 2; l < dm_.n_dec; ++l)
+            for (int h = 0; h < dm_.n_head; ++h) hs.push_back({l, h});
+    if (hs.size() > 512) throw std::invalid_argument("more than 512 alignment heads");
+    std::set<std::pair<int, int>> seen;
+    for (const auto& lh : hs) {
+        if (lh.first < 0 || lh.first >= dm_.n_dec || lh.second < 0 || lh.second >= dm_.n_head)
+            throw std::invalid_argument("alignment head out of range");
+        if (!seen.insert(lh).second) throw std::invalid_argument("duplicate alignment head");
+    }
+    std::stable_sort(hs.begin(), hs.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
+    align_heads_ = hs;
+    align_off_.assign(dm_.n_dec, 0);
+    align_cnt_.assign(dm_.n_dec, 0);
+    for (size_t i = 0; i < hs.size(); ++i) {
+        if (align_cnt_[hs[i].first]++ == 0) align_off_[hs[i].first] = (int)i;
+    }
+    if (al_heads_dev_) upload_alignment_heads();
+}
+
+void Engine::upload_alignment_heads() {
+    select();
+    if (!al_heads_dev_) HIP_CHECK(hipMalloc((void**)&al_heads_dev_, 512 * sizeof(int)));
+    std::vector<int> h(512, 0);
+    for (size_t i = 0; i < align_heads_.size(); ++i) h[i] = align_heads_[i].second;
+    HIP_CHECK(hipMemcpy(al_heads_dev_, h.data(), 512 * sizeof(int), hipMemcpyHostToDevice));
+}
+
+void Engine::align(const std::vector<AlignSeq>& seqs, int n_skip, std::vector<AlignPath>* out) {
+    select();
+    require_weights();
+    out->assign(seqs.size(), AlignPath());
+    if (seqs.empty()) return;
+    const int E = enc_E_, ctx = dm_.n_text_ctx, T = dm_.n_audio_ctx, d = dm_.d;
+    if (E < 1) throw std::runtime_error("align before encode_windows");
+    if (T > kAlignMaxKeys) throw std::runtime_error("align: n_audio_ctx above the alignment kernels' keys");
+    if (align_heads_.empty()) set_alignment_heads({});
+    if (!al_heads_dev_) upload_alignment_heads();
+    const int A = (int)align_heads_.size();
+    const Specials sp = specials_for(dm_.n_vocab);
+    int L = 0, Mmax = 0;
+    for (const AlignSeq& s : seqs) {
+        if (s.window < 0 || s.window >= E) throw std::runtime_error("align: a window that was not encoded");
+        if (n_skip < 0 || (int)s.tokens.size() <= n_skip || (int)s.tokens.size() > ctx)
+            throw std::runtime_error("align: replay length out of range");
+        if (s.M < 1 || s.M > T) throw std::runtime_error("align: keys kept out of range");
+        for (int t : s.tokens)
+            if (t < 0 || t >= dm_.n_vocab) throw std::runtime_error("align: token out of the vocabulary");
+        L = std::max(L, (int)s.tokens.size());
+        Mmax = std::max(Mmax, s.M);
+    }
+    const int N_cap = L - n_skip, M_cap = (Mmax + 7) / 8 * 8;
+    if (N_cap > kAlignMaxRows) throw std::runtime_error("align: more than 256 text rows");
+    align_prepare(N_cap, M_cap);
+    // sequences per replay: the pass's rows, and a workspace of at most 2 GiB of probabilities
+    const int64_t per_seq = (int64_t)A * N_cap * M_cap;
+    const int Bmax = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(max_batch_, max_rows_), ((int64_t)1 << 29) / per_seq));
+    const int B0 = std::min<int>(Bmax, (int)seqs.size());
+    DecGroup& g = groups_[0];
+    HIP_CHECK(hipStreamSynchronize(st_));
+    HIP_CHECK(hipStreamSynchronize(g.st));
+    const int64_t n_int = (int64_t)B0 * (3 + N_cap + N_cap + M_cap);
+    void* pp = al_p_;
+    ensure_capacity(&pp, &al_p_cap_, B0 * per_seq, 4, "alignment probabilities");
+    al_p_ = (float*)pp;
+    pp = al_stat_;
+    ensure_capacity(&pp, &al_stat_cap_, (int64_t)B0 * A * 2 * M_cap, 4, "alignment statistics");
+    al_stat_ = (float*)pp;
+    pp = al_m_;
+    ensure_capacity(&pp, &al_m_cap_, (int64_t)B0 * N_cap * M_cap, 4, "alignment matrix");
+    al_m_ = (float*)pp;
+    pp = al_int_;
+    ensure_capacity(&pp, &al_int_cap_, n_int, 4, "alignment paths");
+    al_int_ = (int*)pp;
+    struct TapOff {  // the tap never outlives the call, nor does the fused launch come back on by it
+        Engine* e;
+        ~TapOff() { e->tap_ = nullptr; }
+    } tap_off{this};
+    xq_on_ = false;
+    align_passes_ = 0;
+    std::vector<int> back;
+    for (size_t s0 = 0; s0 < seqs.size(); s0 += B0) {
+        const int B = (int)std::min<size_t>(B0, seqs.size() - s0);
+        const int cmax = std::max(1, std::min(4, max_rows_ / B));
+        int* dN = al_int_;
+        int* dM = dN + B;
+        int* dlen = dM + B;
+        int* djump = dlen + B;
+        int* dpath = djump + (size_t)B * N_cap;
+        // host image of every upload of this replay: N, M, the window map, then each pass's tokens
+        al_host_.assign((size_t)3 * B + (size_t)B * (L + 4), sp.eot);
+        for (int b = 0; b < B; ++b) {
+            const AlignSeq& s = seqs[s0 + b];
+            al_host_[b] = (int)s.tokens.size() - n_skip;
+            al_host_[B + b] = s.M;
+            al_host_[2 * B + b] = s.window;
+        }
+        g.b0 = 0;
+        g.B = B;
+        g.share = 1;  // one row per window run: the mapped cross-attention, whatever the rows' windows
+        HIP_CHECK(hipMemcpyAsync(dN, al_host_.data(), (size_t)2 * B * 4, hipMemcpyHostToDevice, g.st));
+        HIP_CHECK(hipMemcpyAsync(g.kvrow, al_host_.data() + 2 * B, (size_t)B * 4, hipMemcpyHostToDevice, g.st));
+        dec_reset(g.ds, g.arrive, g.st);
+        AlignTap tap{0, al_p_, A, N_cap, M_cap, dM};
+        tap_ = &tap;
+        int* h = al_host_.data() + 3 * B;
+        for (int c0 = 0; c0 < L; c0 += cmax) {
+            const int n = std::min(cmax, L - c0);
+            for (int b = 0; b < B; ++b)
+                for (int t = 0; t < n; ++t) {
+                    const std::vector<int>& tk = seqs[s0 + b].tokens;
+                    h[b * n + t] = c0 + t < (int)tk.size() ? tk[c0 + t] : sp.eot;  // padding: causal, so it reaches no earlier row
+                }
+            HIP_CHECK(hipMemcpyAsync(g.tok_in, h, (size_t)B * n * 4, hipMemcpyHostToDevice, g.st));
+            h += B * n;
+            dec_embed(dt_, g.tok_in, B * n, n, d, tok_emb_, tok_q_, dec_pos_, g.ds, g.dx, g.st);
+            tap.row0 = c0 - n_skip;
+            enqueue_layers(g, E, n);
+            dec_advance(g.ds, n, g.st);
+            ++align_passes_;
+        }
+        tap_ = nullptr;
+        align_norm(al_p_, B, A, N_cap, M_cap, dN, dM, al_stat_, al_m_, g.st);
+        align_dtw(al_m_, B, N_cap, M_cap, dN, dM, djump, dlen, dpath, g.st);
+        back.assign((size_t)B * (1 + N_cap), 0);
+        HIP_CHECK(hipMemcpyAsync(back.data(), dlen, back.size() * 4, hipMemcpyDeviceToHost, g.st));  // len, then jump
+        HIP_CHECK(hipStreamSynchronize(g.st));
+        for (int b = 0; b < B; ++b) {
+            AlignPath& o = (*out)[s0 + b];
+            const int N = (int)seqs[s0 + b].tokens.size() - n_skip;
+            o.len = back[b];
+            o.jump.assign(back.begin() + B + (size_t)b * N_cap, back.begin() + B + (size_t)b * N_cap + N);
+        }
+        al_last_[0] = B - 1;
+        al_last_[1] = (int)seqs[s0 + B - 1].tokens.size() - n_skip;
+        al_last_[2] = seqs[s0 + B - 1].M;
+        al_last_[3] = N_cap;
+        al_last_[4] = M_cap;
+        al_last_B_ = B;
+        al_last_A_ = A;
+    }
+}
+
+bool Engine::align_last(int* A_out, int* N_out, int* M_out, std::vector<float>* p, std::vector<float>* m,
+                        std::vector<int>* path) {
+    if (al_last_[0] < 0) return false;
+    select();
+    const int b = al_last_[0], N = al_last_[1], M = al_last_[2], N_cap = al_last_[3], M_cap = al_last_[4];
+    const int A = al_last_A_, B = al_last_B_;
+    *A_out = A; *N_out = N; *M_out = M;
+    HIP_CHECK(hipDeviceSynchronize());
+    if (p) {
+        p->assign((size_t)A * N * M, 0.0f);
+        for (int a = 0; a < A; ++a)
+            HIP_CHECK(hipMemcpy2D(p->data() + (size_t)a * N * M, (size_t)M * 4, al_p_ + (((size_t)b * A + a) * N_cap) * M_cap,
+                                  (size_t)M_cap * 4, (size_t)M * 4, N, hipMemcpyDeviceToHost));
+    }
+    if (m) {
+        m->assign((size_t)N * M, 0.0f);
+        HIP_CHECK(hipMemcpy2D(m->data(), (size_t)M * 4, al_m_ + (size_t)b * N_cap * M_cap, (size_t)M_cap * 4, (size_t)M * 4, N,
+                              hipMemcpyDeviceToHost));
+    }
+    if (path) {
+        int len = 0;
+        HIP_CHECK(hipMemcpy(&len, al_int_ + 2 * B + b, 4, hipMemcpyDeviceToHost));
+        len = std::max(0, std::min(len, N_cap + M_cap));
+        std::vector<int> raw((size_t)len);
+        const int* dpath = al_int_ + 3 * B + (size_t)B * N_cap + (size_t)b * (N_cap + M_cap);
+        if (len) HIP_CHECK(hipMemcpy(raw.data(), dpath, (size_t)len * 4, hipMemcpyDeviceToHost));
+        path->assign((size_t)len * 2, 0);
+        for (int i = 0; i < len; ++i) {  // stored backwards, (row << 16) | key
+            const int v = raw[(size_t)len - 1 - i];
+            (*path)[2 * i] = (int16_t)(v >> 16);
+            (*path)[2 * i + 1] = (int16_t)(v & 0xFFFF);
+        }
+    }
+    return true;
 }
 
 // phase times of the stages since the last decode (HIP events; read after its synchronisation)

@@ -146,6 +146,30 @@ public:
     void beam_begin(int B, const DecodeRequest& rq, BeamCands* out, int* lang_out);
     void beam_next(const int* src, const int* tokens, const int* rowstate, int step, BeamCands* out);
 
+    // ---- token alignment from the cross-attention
+    // the alignment heads as (layer, head) pairs; none: every head of the top half of the decoder
+    // layers.  Throws std::invalid_argument on a pair out of range, a duplicate, or more than 512.
+    void set_alignment_heads(const std::vector<std::pair<int, int>>& pairs);
+    int alignment_heads() const { return (int)align_heads_.size(); }
+    struct AlignSeq {
+        int window;               // its cross K/V row of the last encode_windows
+        std::vector<int> tokens;  // the replay's inputs [sot, (lang, task,) notimestamps, text ...]
+        int M;                    // keys kept: n_frames / 2
+    };
+    struct AlignPath {
+        std::vector<int> jump;    // the first key of each row on the path (the rows: inputs n_skip ..)
+        int len = 0;
+    };
+    // One teacher-forced replay of each finished window through the chunked prefill (eager, never on the
+    // fused cross-Q launch) with align_qk after every tapped layer's cross-Q, then align_norm and
+    // align_dtw, and one read-back.  Uses decode group 0's self-K/V cache and step state: call it only
+    // when the round's decode results are on the host.
+    void align(const std::vector<AlignSeq>& seqs, int n_skip, std::vector<AlignPath>* out);
+    int align_passes() const { return align_passes_; }          // replay passes of the last align()
+    int64_t align_workspace_bytes() const { return (al_p_cap_ + al_stat_cap_ + al_m_cap_ + al_int_cap_) * 4; }
+    // the last aligned sequence: p [A][N][M], m [N][M], path [len][2]; false before any alignment
+    bool align_last(int* A, int* N, int* M, std::vector<float>* p, std::vector<float>* m, std::vector<int>* path);
+
     // the normalised log-mel [n_mels][3000] of the window at frame `seek` of one utterance
     void debug_mel(const float* pcm_host, int n, int seek, float* out_host);
     void debug_encode(const float* mel_host, float* out_host);
@@ -272,6 +296,26 @@ private:
     // its event pair per layer
     int probe_kind_ = -1;
     std::vector<hipEvent_t> probe_ev_;
+    // align(): read by enqueue_layers as probe_kind_ is.  After the unfused cross-Q GEMV of a layer that
+    // has alignment heads it launches align_qk on g.dq; nullptr (every other call): nothing is enqueued.
+    struct AlignTap {
+        int row0;                 // text row of the pass's first input (negative inside the prompt)
+        float* p; int A, N_cap, M_cap;
+        const int* M;
+    };
+    const AlignTap* tap_ = nullptr;
+    std::vector<std::pair<int, int>> align_heads_;   // sorted by layer (the caller's order within one)
+    std::vector<int> align_off_, align_cnt_;         // per decoder layer: its run of align_heads_
+    int* al_heads_dev_ = nullptr;                    // [512] the heads of align_heads_
+    // the alignment workspace, outside the arenas (allocated by the first align(), grown on demand)
+    float *al_p_ = nullptr, *al_stat_ = nullptr, *al_m_ = nullptr;
+    int* al_int_ = nullptr;                          // N [B], M [B], len [B], jump [B][N_cap], path [B][N_cap + M_cap]
+    int64_t al_p_cap_ = 0, al_stat_cap_ = 0, al_m_cap_ = 0, al_int_cap_ = 0;
+    std::vector<int> al_host_;                       // host source of the alignment's uploads
+    int align_passes_ = 0;
+    int al_last_[5] = {-1, 0, 0, 0, 0};              // sequence in the workspace, N, M, N_cap, M_cap
+    int al_last_B_ = 0, al_last_A_ = 0;
+    void upload_alignment_heads();
 
     // ---- weights (one arena)
     char* warena_ = nullptr;

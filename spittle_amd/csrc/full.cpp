@@ -242,8 +242,14 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
     const char* ns_env = getenv("SPT_NO_WINDOW_SHARE");
     const bool no_share = ns_env && atoi(ns_env) != 0;
     std::map<int, int> chunk_utt;  // utterance -> its index in the loaded set
+    if (p.token_timestamps && no_share) throw std::invalid_argument("token timestamps need the shared windows");
+    if (p.forced && p.n_forced > 0 && p.beam_size > 1) throw std::invalid_argument("forced tokens with beam search");
+    struct Kept {  // a window's kept decoder, to be aligned before the next encoder run
+        int u, base, len, seek;
+    };
     auto window_pass = [&](const std::vector<int>& chunk, const std::map<int, int>& win_of) {
         std::vector<int> pending = chunk;
+        std::vector<Kept> kept;
         for (size_t it = 0; it < temps.size() && !pending.empty(); ++it) {
             const float t_cur = temps[it];
             const bool beam = p.beam_size > 1 && t_cur == 0.0f;  // WHISPER_SAMPLING_BEAM_SEARCH
@@ -277,7 +283,8 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                     DecodeRequest rq;
                     rq.prompt = prompt_init;
                     rq.full = true;
-                    rq.flags = (p.suppress_blank ? 1u : 0u) | (p.no_timestamps ? 2u : 0u);
+                    rq.flags = (p.suppress_blank ? 1u : 0u) | (p.no_timestamps ? 2u : 0u) | (p.ignore_eot ? 4u : 0u);
+                    std::vector<int32_t> forced_rows;  // one row of the utterance's forced tokens per decoder row
                     rq.ts.temperature = t_cur;
                     rq.ts.suppress_blank = p.suppress_blank ? 1 : 0;
                     rq.ts.no_ts = p.no_timestamps ? 1 : 0;
@@ -296,7 +303,14 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                             rq.seek_end.push_back(us[u].seek_end);
                             if (P > 0) rq.row_prefix.push_back(prefix[u]);
                             if (multi) rq.lang_tok.push_back(us[u].lang >= 0 ? us[u].lang : -(j * nd + 1));
+                            if (p.forced && p.n_forced > 0)
+                                forced_rows.insert(forced_rows.end(), p.forced + (size_t)u * p.n_forced,
+                                                   p.forced + (size_t)(u + 1) * p.n_forced);
                         }
+                    }
+                    if (!forced_rows.empty()) {
+                        rq.forced = forced_rows.data();
+                        rq.n_forced = p.n_forced;
                     }
                     if (no_share) {  // test hook: every row its own copy of its window (ABI <= 10)
                         std::vector<int> wu, ws;
@@ -380,6 +394,11 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                 r.tid.insert(r.tid.end(), bd.tid.begin(), bd.tid.begin() + len);
                 r.n_windows++;
                 r.n_fallbacks += (int)it;
+                if (p.token_timestamps) {
+                    r.tok_t0.resize(r.tokens.size(), -1);
+                    r.tok_t1.resize(r.tokens.size(), -1);
+                    kept.push_back(Kept{u, base, len, us_u.seek});
+                }
                 // prompt_past: the conditioning tokens just used (without [prev]) + the result
                 const std::vector<int>& pf = prefix[u];
                 std::vector<int> past;
@@ -412,6 +431,45 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                 us_u.seek += bd.seek_delta > 0 ? bd.seek_delta : 3000;
             }
             pending.swap(again);
+        }
+        // token timestamps: one replay of every window finalised above, while their cross K/V is still
+        // the encoder's last output (a window that fell back is aligned once, for the decoder kept)
+        std::vector<Engine::AlignSeq> seqs;
+        std::vector<const Kept*> who;
+        std::vector<std::vector<int>> text_at;  // each sequence's text tokens: their indices in the result
+        for (const Kept& k : kept) {
+            const FullResult& r = (*out)[k.u];
+            Engine::AlignSeq s;
+            s.window = win_of.at(k.u);
+            s.tokens = {sp.sot};
+            if (multi) {
+                s.tokens.push_back(us[k.u].lang >= 0 ? us[k.u].lang : sp.sot + 1);
+                s.tokens.push_back(p.translate ? sp.translate : sp.transcribe);
+            }
+            s.tokens.push_back(sp.not_);
+            std::vector<int> at;
+            for (int i = 0; i < k.len; ++i)
+                if (r.tokens[k.base + i] < sp.eot) {
+                    s.tokens.push_back(r.tokens[k.base + i]);
+                    at.push_back(k.base + i);
+                }
+            if (at.empty()) continue;  // timestamp tokens and eot only: no alignment
+            s.M = std::min(3000, us[k.u].seek_end - k.seek) / 2;
+            seqs.push_back(std::move(s));
+            who.push_back(&k);
+            text_at.push_back(std::move(at));
+        }
+        if (!seqs.empty()) {
+            std::vector<Engine::AlignPath> paths;
+            e.align(seqs, multi ? 3 : 1, &paths);
+            for (size_t i = 0; i < seqs.size(); ++i) {
+                FullResult& r = (*out)[who[i]->u];
+                const std::vector<int>& jump = paths[i].jump;  // rows: each text token, then the end
+                for (size_t t = 0; t < text_at[i].size(); ++t) {
+                    r.tok_t0[text_at[i][t]] = who[i]->seek + 2 * (int64_t)jump[t];
+                    r.tok_t1[text_at[i][t]] = who[i]->seek + 2 * (int64_t)jump[t + 1];
+                }
+            }
         }
     };
     // utterances in sets whose PCM and log-mel stay resident together (an hour of audio per set;

@@ -39,6 +39,15 @@ struct FullParams {  // whisper_full_params
     int max_tokens = 0;
     int n_max_text_ctx = 16384;
     uint64_t seed = 0;
+    // DTW token timestamps from the alignment heads' cross-attention: one extra replay of
+    // each window's kept decoder; fills FullResult::tok_t0 / tok_t1 and changes nothing else
+    bool token_timestamps = false;
+    // test hooks of the aligned call: teacher forcing (forced [utterances][n_forced]: the token fed after
+    // step s of every window of utterance u is forced[u][s]; the token recorded stays the sampler's) and
+    // SPT_IGNORE_EOT (no early exit from the pass loop).  Not with beam search.
+    const int32_t* forced = nullptr;
+    int n_forced = 0;
+    bool ignore_eot = false;
 };
 
 struct FullSegment {
@@ -50,6 +59,9 @@ struct FullSegment {
 struct FullResult {
     std::vector<int> tokens;        // every window's chosen decoder, result_len tokens each
     std::vector<float> plog, tid;   // per token: log-probability, timestamp id
+    // FullParams::token_timestamps: per token (index-aligned with tokens) its start and end in 10 ms
+    // units, -1 for timestamp and eot tokens; empty otherwise
+    std::vector<int64_t> tok_t0, tok_t1;
     std::vector<FullSegment> segments;
     std::string text;               // concatenated segment texts
     int n_windows = 0;

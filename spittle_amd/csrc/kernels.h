@@ -308,4 +308,38 @@ void dec_kv_gather(int dtype, const void* src, void* dst, const int* rows, int L
 // pos0 += n (after a prefill pass that produces no token)
 void dec_advance(DecState* ds, int n, hipStream_t st);
 
+// ------------------------------------------------------------------ token alignment (k_align.hip)
+// The workspace of an alignment: p [B][A][N_cap][M_cap] f32 (sequence, alignment head, text row, key),
+// stat [B][A][2][M_cap], m [B][N_cap][M_cap]; N [B] and M [B] (device) are each sequence's rows and
+// keys in use (clamped to the caps by every kernel).
+constexpr int kAlignMaxKeys = 3072;  // align_qk: T_enc (its scores of 4 rows: 48 KiB of LDS)
+constexpr int kAlignMaxRows = 256;   // align_dtw: one thread per text row
+struct AlignQkArgs {
+    const void* q;            // [B * Tq][H * 64], engine dtype: the cross-Q rows of one pass
+    int Tq, pos0;             // 1..4 rows per sequence, row t is text row pos0 + t (rows below 0 are skipped)
+    const void* kv;           // one decoder layer of the cross K/V cache (kv_offset layout)
+    int B_layout, H, T_enc;
+    const int* kvrow;         // device [B]: sequence b attends to window kvrow[b] (nullptr: window b)
+    const int* heads;         // device [n_heads]: this layer's alignment heads, any order
+    int n_heads, a0;          // heads[i] is head a0 + i of p
+    float* p; int A, N_cap, M_cap;
+    const int* M;
+};
+// p[b][a0 + i][pos0 + t][0 .. M[b]) = softmax over all T_enc real keys of q . k / 8 (f32, maximum
+// subtracted; the keys that pad the last 32-key block take no part)
+void align_qk(int dtype, const AlignQkArgs& a, int B, hipStream_t st);
+// stat = per-column mean and population std over the rows; m = the head mean (head order) of the
+// 7-tap median along the keys (reflect padding, none for M <= 3) of (p - mean) / std (0 where std == 0)
+void align_norm(const float* p, int B, int A, int N_cap, int M_cap, const int* N, const int* M, float* stat, float* m,
+                hipStream_t st);
+// dynamic time warping of -m, one workgroup per sequence (HF _dynamic_time_warping's recurrence, tie
+// rule and backtrace, f32): jump [B][N_cap] = first key of each row on the path, len [B] = path
+// length, path (optional) [B][N_cap + M_cap] = the path backwards, (row << 16) | (key & 0xFFFF).
+// N_cap <= 256, M_cap a multiple of 8, 2 bits per cell within 160 KiB of LDS (226 x 1504 is 85 KiB).
+void align_dtw(const float* m, int B, int N_cap, int M_cap, const int* N, const int* M, int* jump, int* len, int* path,
+               hipStream_t st);
+// the > 64 KiB dynamic-LDS attribute of align_dtw for these caps (throws on caps it cannot run);
+// call before any stream capture
+void align_prepare(int N_cap, int M_cap);
+
 }  // namespace spt

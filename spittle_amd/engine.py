@@ -94,6 +94,10 @@ class TranscriptionResult:
     n_windows: int = 0
     language: Optional[str] = None      # ISO-639-1 code decoded with (detected or given)
     n_fallbacks: int = 0                # temperature fallbacks taken (repeated decodes)
+    # transcribe_*_aligned only: (index into tokens, t0, t1, p) per text token, in 10 ms units, and
+    # (text, t0, t1, p, first entry of token_times, count) per word
+    token_times: Optional[list] = None
+    words: Optional[list] = None
 
 
 def _infer_params(p: Optional[WhisperInferenceParams], keep: list) -> L.InferParams:
@@ -225,6 +229,66 @@ class WhisperEngine:
         out = (C.POINTER(L.Result) * n)()
         self._check(self._lib.spt_transcribe_batch(self._ctx, ptrs, lens, n, C.byref(ip), out))
         return [_take_result(out[i]) for i in range(n)]
+
+    # -- DTW token and word timestamps (SPT_HAS_TOKEN_TIMESTAMPS) ------------
+    def set_alignment_heads(self, pairs: Sequence = ()) -> None:
+        """The alignment heads as (layer, head) pairs; none restores the default (every head of the top
+        half of the decoder layers)."""
+        self._need()
+        a = np.ascontiguousarray(np.asarray(list(pairs), np.int32).reshape(-1, 2))
+        self._check(self._lib.spt_set_alignment_heads(self._ctx, a.ctypes.data_as(C.POINTER(C.c_int32)), a.shape[0]))
+
+    def transcribe_samples_aligned(self, samples, params: Optional[WhisperInferenceParams] = None) -> TranscriptionResult:
+        return self.transcribe_batch_aligned([samples], params)[0]
+
+    def transcribe_batch_aligned(self, batch: Sequence, params: Optional[WhisperInferenceParams] = None):
+        """transcribe_batch on the whisper_full path; each result also carries ``token_times`` -- one
+        (index into tokens, t0, t1, p) per text token, in 10 ms units -- and ``words`` -- (text, t0, t1,
+        p, first entry of token_times, count), for models with a vocabulary."""
+        self._need()
+        keep: list = []
+        ip = _infer_params(params, keep)
+        arrs = [np.ascontiguousarray(np.asarray(s, dtype=np.float32).reshape(-1)) for s in batch]
+        n = len(arrs)
+        ptrs = (C.POINTER(C.c_float) * n)(*[a.ctypes.data_as(C.POINTER(C.c_float)) for a in arrs])
+        lens = (C.c_size_t * n)(*[a.size for a in arrs])
+        out = (C.POINTER(L.Result) * n)()
+        al = (C.POINTER(L.Alignment) * n)()
+        self._check(self._lib.spt_transcribe_aligned_batch(self._ctx, ptrs, lens, n, C.byref(ip), out, al))
+        res = []
+        for i in range(n):
+            r = _take_result(out[i])
+            a = al[i].contents
+            r.token_times = [(a.tokens[k].index, a.tokens[k].t0, a.tokens[k].t1, a.tokens[k].p) for k in range(a.n_tokens)]
+            r.words = [((a.words[k].text or b"").decode("utf-8", "replace"), a.words[k].t0, a.words[k].t1, a.words[k].p,
+                        a.words[k].i0, a.words[k].n_tokens) for k in range(a.n_words)]
+            self._lib.spt_alignment_free(al[i])
+            res.append(r)
+        return res
+
+    def align_stats(self) -> dict:
+        """What the last aligned call recorded: replay passes of its last alignment, alignment heads in
+        use, bytes of the alignment workspace held (spt_debug_align_stats)."""
+        self._need()
+        n, h, b = C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self._lib.spt_debug_align_stats(self._ctx, C.byref(n), C.byref(h), C.byref(b)))
+        return {"replay_passes": n.value, "alignment_heads": h.value, "workspace_bytes": b.value}
+
+    def debug_align_last(self):
+        """The last aligned window: (p [heads][rows][keys], m [rows][keys], path [len][2])."""
+        self._need()
+        A, N, M, ln = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        fp0, ip0 = C.POINTER(C.c_float)(), C.POINTER(C.c_int32)()
+        self._check(self._lib.spt_debug_align_last(self._ctx, C.byref(A), C.byref(N), C.byref(M), fp0, 0, fp0, 0, ip0, 0,
+                                                   C.byref(ln)))
+        p = np.zeros((A.value, N.value, M.value), np.float32)
+        m = np.zeros((N.value, M.value), np.float32)
+        path = np.zeros((N.value + M.value, 2), np.int32)
+        self._check(self._lib.spt_debug_align_last(self._ctx, C.byref(A), C.byref(N), C.byref(M),
+                                                   p.ctypes.data_as(C.POINTER(C.c_float)), p.size,
+                                                   m.ctypes.data_as(C.POINTER(C.c_float)), m.size,
+                                                   path.ctypes.data_as(C.POINTER(C.c_int32)), path.size, C.byref(ln)))
+        return p, m, path[:ln.value].copy()
 
     def transcribe_batch_device(self, dev_ptr: int, stride: int, lengths: Sequence[int],
                                 params: Optional[WhisperInferenceParams] = None):
