@@ -390,6 +390,43 @@ spt_status spt_debug_xq_fused(int32_t device, int32_t dtype, const float* x, con
                               const float* wq, const float* bias, const float* k, const float* v, float pad_value,
                               int32_t B, int32_t H, int32_t T_enc, int32_t lds, int32_t touch, float* q, float* out,
                               char* err, size_t errlen);
+/* The GEMM tiles and the LayerNorm kernels alone (additive over ABI 14): one launch of
+ * the engine's launcher on caller-supplied host f32 arrays, on a stream of its own on `device`.  A call
+ * the launcher would refuse, or that would read or write outside a buffer, returns SPT_ERR_INVALID_ARG
+ * with the message in err before any launch; no device: SPT_ERR_DEVICE.
+ * spt_debug_gemm: one gemm_nt_variant(dtype, epi, .., batch, variant) call, C = epi(A . W^T).  epi:
+ * 0 bias, 1 bias + GELU, 2 bias + GELU + pos (f32), 3 C += alpha (acc + bias) (f32), 4 the head-split
+ * store into the cross K/V cache, 5 bias + swish, 6 bias + ReLU, 7 alpha (acc + bias) (f32), 8 split-K
+ * slab s at C + s * c_split (f32).  variant: 0 automatic, 1 128 x 128, 2 256 x 256 (bf16 / f16), 3
+ * skinny (M <= 64, bf16 / f16, batch 1), 4 64 x 128, 5 64 x 64.  A and C are flat arrays of a_count /
+ * c_count elements; batch item z's row m starts at a_off + z * sA + m * lda (rows may overlap: lda < K,
+ * the conv stem) and c_off + z * sC + m * ldc.  W [N][ldw], bias [N] or NULL, pos [M][N] or NULL.  A
+ * and W are rounded to dtype on the host.  C is in and out: the caller's values are uploaded (rounded
+ * to dtype for the epilogues that store dtype: 0, 1, 4, 5, 6), the launch runs, the whole buffer comes
+ * back as f32 -- epilogue 3 reads the caller's residual, and every element the kernel must not touch
+ * is the caller's to inspect.  Epilogue 4: C is the cache of N / (2 * kv_H * 64) layers of
+ * ceil(kv_T / 32) * kv_B * kv_H * 4096 elements from c_off, M == kv_B * kv_T.  Also refused: the 16-byte
+ * alignment the kernel that would run needs of A, W, C, pos and their strides, variant 3 with
+ * batch != 1, an epilogue a variant lacks, epilogues 4 and 8 with batch != 1. */
+spt_status spt_debug_gemm(int32_t device, int32_t dtype, int32_t epi, int32_t variant, int32_t batch, int32_t M,
+                          int32_t N, int32_t K, const float* A, int64_t a_count, int64_t a_off, int32_t lda, int64_t sA,
+                          const float* W, int32_t ldw, const float* bias, const float* pos, float* C, int64_t c_count,
+                          int64_t c_off, int32_t ldc, int64_t sC, float alpha, int32_t ksplit, int64_t c_split,
+                          int32_t kv_B, int32_t kv_T, int32_t kv_H, char* err, size_t errlen);
+/* spt_debug_layernorm: x [M][d] f32, w, b [d]; eps 1e-5.  mode: */
+enum {
+    SPT_LN_PLAIN = 0, /* layernorm: y [M][d] = LN(x) w + b, stored as dtype */
+    SPT_LN_PEND = 1,  /* layernorm_pend: v = x + alpha (slab_0 + .. + slab_{ks-1} + pbias), y = LN(v) w + b as
+                         dtype; x comes back (v where write_x != 0, else as given) */
+    SPT_LN_PEND2 = 2  /* layernorm_pend2: y [M][d] f32 = LN(v) w + b, y2 = LN(y) w2 + b2 as dtype; ks 1, 2, 4, 8 */
+};
+/* The slabs are a flat array of slab_count elements, slab q's row m at q * slab_stride + m * d.  Refused:
+ * d % 4, d above 1536 (mode 2: 1024), a NULL pbias in modes 1 and 2, slabs outside the array,
+ * slab_stride % 4. */
+spt_status spt_debug_layernorm(int32_t device, int32_t dtype, int32_t mode, float* x, int32_t M, int32_t d,
+                               const float* slab, int64_t slab_count, int32_t ks, int64_t slab_stride,
+                               const float* pbias, float alpha, const float* w, const float* b, const float* w2,
+                               const float* b2, int32_t write_x, float* y, float* y2, char* err, size_t errlen);
 
 /* DTW token and word timestamps from the alignment heads' cross-attention (additive over ABI 14,
  * announced by SPT_HAS_TOKEN_TIMESTAMPS): whisper.cpp's dtw_token_timestamps, OpenAI's

@@ -435,6 +435,62 @@ extern "C" {
         err: *mut c_char,
         errlen: usize,
     ) -> spt_status;
+    // the GEMM tiles and LayerNorm kernels alone (test hooks, additive over ABI 14); mode: SPT_LN_*
+    pub fn spt_debug_gemm(
+        device: i32,
+        dtype: i32,
+        epi: i32,
+        variant: i32,
+        batch: i32,
+        m: i32,
+        n: i32,
+        k: i32,
+        a: *const f32,
+        a_count: i64,
+        a_off: i64,
+        lda: i32,
+        s_a: i64,
+        w: *const f32,
+        ldw: i32,
+        bias: *const f32,
+        pos: *const f32,
+        c: *mut f32,
+        c_count: i64,
+        c_off: i64,
+        ldc: i32,
+        s_c: i64,
+        alpha: f32,
+        ksplit: i32,
+        c_split: i64,
+        kv_b: i32,
+        kv_t: i32,
+        kv_h: i32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_layernorm(
+        device: i32,
+        dtype: i32,
+        mode: i32,
+        x: *mut f32,
+        m: i32,
+        d: i32,
+        slab: *const f32,
+        slab_count: i64,
+        ks: i32,
+        slab_stride: i64,
+        pbias: *const f32,
+        alpha: f32,
+        w: *const f32,
+        b: *const f32,
+        w2: *const f32,
+        b2: *const f32,
+        write_x: i32,
+        y: *mut f32,
+        y2: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
     // DTW token and word timestamps (SPT_HAS_TOKEN_TIMESTAMPS, additive over ABI 14)
     pub fn spt_set_alignment_heads(ctx: *mut spt_ctx, layer_head: *const i32, n_pairs: i32) -> spt_status;
     pub fn spt_transcribe_aligned(

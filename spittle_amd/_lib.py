@@ -61,6 +61,8 @@ EXPORTS = [
     "spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather",
     # the attention kernels alone (test hooks, additive over ABI 14)
     "spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross", "spt_debug_xq_fused",
+    # the GEMM tiles and LayerNorm kernels alone (test hooks, additive over ABI 14)
+    "spt_debug_gemm", "spt_debug_layernorm",
     # quantised decoder weights resident in HBM (SPT_HAS_QUANT_RESIDENT)
     "spt_debug_qgemv", "spt_get_weight_residency",
     # the token-alignment kernels alone (SPT_HAS_ALIGN_KERNELS)
@@ -89,6 +91,7 @@ SPT_GGML_Q4_1, SPT_GGML_Q5_0, SPT_GGML_Q5_1 = 3, 6, 7
 SPT_GV_BIAS, SPT_GV_BIAS_GELU, SPT_GV_PARTIAL, SPT_GV_QKV_CACHE, SPT_GV_LOGITS, SPT_GV_BIAS_RESID = range(6)
 SPT_QGEMV_A_DIRECT, SPT_QGEMV_A_LN = 0, 1
 SPT_ATTN_CROSS_8WAVE, SPT_ATTN_CROSS_VW, SPT_ATTN_CROSS_VW_PQ, SPT_ATTN_CROSS_VW_MERGE, SPT_ATTN_CROSS_VW_PQ_MERGE = range(5)
+SPT_LN_PLAIN, SPT_LN_PEND, SPT_LN_PEND2 = range(3)
 SPT_SV_LANG_AUTO, SPT_SV_LANG_ZH, SPT_SV_LANG_EN, SPT_SV_LANG_YUE, SPT_SV_LANG_JA, SPT_SV_LANG_KO = range(6)
 SPT_PK_WEIGHTS_EMPTY = 1
 SPT_PK_TS_TOKEN, SPT_PK_TS_WORD, SPT_PK_TS_SEGMENT = 0, 1, 2
@@ -451,6 +454,14 @@ def load():
     L.spt_debug_xq_fused.argtypes = [i32, i32, fp, fp, fp, fp, fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, fp, fp,
                                      C.c_char_p, C.c_size_t]
     for fn in ("spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross", "spt_debug_xq_fused"):
+        getattr(L, fn).restype = C.c_int
+    # the GEMM tiles and LayerNorm kernels alone
+    i64 = C.c_int64
+    L.spt_debug_gemm.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, fp, i64, i64, i32, i64, fp, i32, fp, fp, fp, i64,
+                                 i64, i32, i64, C.c_float, i32, i64, i32, i32, i32, C.c_char_p, C.c_size_t]
+    L.spt_debug_layernorm.argtypes = [i32, i32, i32, fp, i32, i32, fp, i64, i32, i64, fp, C.c_float, fp, fp, fp, fp, i32,
+                                      fp, fp, C.c_char_p, C.c_size_t]
+    for fn in ("spt_debug_gemm", "spt_debug_layernorm"):
         getattr(L, fn).restype = C.c_int
     L.spt_debug_qgemv.argtypes = [i32, i32, i32, C.c_void_p, C.c_size_t, i32, i32, fp, i32, fp, fp, fp, fp, i32, i32,
                                   i32, fp, fp, fp, fp, fp, C.c_char_p, C.c_size_t]

@@ -21,25 +21,6 @@ namespace {
 
 using namespace spt::dbg;
 
-// host f32 -> device storage of dtype (h16 keeps the rounded copy alive until the stream has read it)
-const void* up_as(Scope& sc, int dtype, const float* v, size_t n, std::vector<uint16_t>& h16) {
-    if (dtype == spt::DT_F32) return sc.up(v, n);
-    h16 = to_half_storage(dtype, v, n);
-    return sc.up(h16.data(), n);
-}
-
-// device storage of dtype -> host f32
-void down_f32(Scope& sc, int dtype, const void* dev, float* h, size_t n) {
-    if (dtype == spt::DT_F32) {
-        sc.down(h, (const float*)dev, n);
-        return;
-    }
-    float* f = sc.alloc<float>(n);
-    spt::to_f32(dtype, dev, f, (int64_t)n, sc.st);
-    SPT_LAUNCH_CHECK();
-    sc.down(h, (const float*)f, n);
-}
-
 void check_dtype(int32_t dtype) {
     if (dtype != spt::DT_F32 && dtype != spt::DT_BF16 && dtype != spt::DT_F16)
         throw std::runtime_error("debug_attn: dtype is f32, bf16 or f16");

@@ -1,6 +1,7 @@
 // capi_debug.h -- what the context-free test hooks share (capi_sample.cpp: spt_debug_sample_*,
-// capi_attn.cpp: spt_debug_attn_*): the error message, the device check, a stream with the buffers
-// of one call, and the host rounding of f32 inputs to an engine dtype.
+// capi_attn.cpp: spt_debug_attn_*, capi_gemm.cpp: spt_debug_gemm, spt_debug_layernorm): the error
+// message, the device check, a stream with the buffers of one call, the host rounding of f32 inputs to
+// an engine dtype and the copies between host f32 and device storage of a dtype.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -72,6 +73,25 @@ inline std::vector<uint16_t> to_half_storage(int dtype, const float* v, size_t n
     std::vector<uint16_t> o(n);
     for (size_t i = 0; i < n; ++i) o[i] = dtype == DT_BF16 ? f2bf(v[i]) : f2h_bits(v[i]);
     return o;
+}
+
+// host f32 -> device storage of dtype (h16 keeps the rounded copy alive until the stream has read it)
+inline const void* up_as(Scope& sc, int dtype, const float* v, size_t n, std::vector<uint16_t>& h16) {
+    if (dtype == DT_F32) return sc.up(v, n);
+    h16 = to_half_storage(dtype, v, n);
+    return sc.up(h16.data(), n);
+}
+
+// device storage of dtype -> host f32
+inline void down_f32(Scope& sc, int dtype, const void* dev, float* h, size_t n) {
+    if (dtype == DT_F32) {
+        sc.down(h, (const float*)dev, n);
+        return;
+    }
+    float* f = sc.alloc<float>(n);
+    to_f32(dtype, dev, f, (int64_t)n, sc.st);
+    SPT_LAUNCH_CHECK();
+    sc.down(h, (const float*)f, n);
 }
 
 }  // namespace dbg

@@ -760,55 +760,36 @@ void gemm_prepare() {
 
 void gemm_nt(int dtype, int epi, const GemmArgs& g, int batch, hipStream_t st) { gemm_nt_variant(dtype, epi, g, batch, 0, st); }
 
-void gemm_nt_variant(int dtype, int epi, const GemmArgs& g, int batch, int variant, hipStream_t st) {
+namespace {
+bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+bool misaligned16(int64_t elems, int esz) { return (elems * esz) % 16 != 0; }
+}  // namespace
+
+// Everything gemm_nt_variant refuses, and the kernel it then launches (1: 128 x 128 ring, 2: 256 x 256,
+// 3: skinny, 4: 64 x 128, 5: 64 x 64).  Host only: it reads the pointers' alignment, never their
+// contents, and needs no device.
+int gemm_nt_plan(int dtype, int epi, const GemmArgs& g, int batch, int variant) {
     const int esz = dtype == DT_F32 ? 4 : 2;
     if (g.ksplit < 1 || g.K % g.ksplit || (g.ksplit > 1 && epi != EPI_PARTIAL))
         throw std::runtime_error("gemm_nt: split-K needs EPI_PARTIAL and K % ksplit == 0");
     if (variant != 3 && (g.N % (variant == 5 ? 64 : BN) != 0 || (g.K / g.ksplit * esz) % SLAB != 0 || g.M <= 0))
         throw std::runtime_error("gemm_nt: unsupported shape M=" + std::to_string(g.M) + " N=" +
                                  std::to_string(g.N) + " K=" + std::to_string(g.K));
-#define SPT_GEMM_CASES(T)                                                          \
-    switch (epi) {                                                                 \
-        case EPI_BIAS: launch_t<T, EPI_BIAS>(g, batch, variant, st); return;       \
-        case EPI_BIAS_GELU: launch_t<T, EPI_BIAS_GELU>(g, batch, variant, st); return; \
-        case EPI_BIAS_GELU_POS: launch_t<T, EPI_BIAS_GELU_POS>(g, batch, variant, st); return; \
-        case EPI_BIAS_RESID: launch_t<T, EPI_BIAS_RESID>(g, batch, variant, st); return; \
-        case EPI_KVSPLIT: launch_t<T, EPI_KVSPLIT>(g, batch, variant, st); return; \
-        case EPI_BIAS_SWISH: launch_t<T, EPI_BIAS_SWISH>(g, batch, variant, st); return; \
-        case EPI_BIAS_RELU: launch_t<T, EPI_BIAS_RELU>(g, batch, variant, st); return; \
-        case EPI_BIAS_F32: launch_t<T, EPI_BIAS_F32>(g, batch, variant, st); return; \
-        case EPI_PARTIAL: launch_t<T, EPI_PARTIAL>(g, batch, variant, st); return; \
-    }
-#define SPT_GEMM256_CASES(F)                                                       \
-    switch (epi) {                                                                 \
-        case EPI_BIAS: launch_256<EPI_BIAS, F>(g, batch, st); return;              \
-        case EPI_BIAS_GELU: launch_256<EPI_BIAS_GELU, F>(g, batch, st); return;    \
-        case EPI_BIAS_GELU_POS: launch_256<EPI_BIAS_GELU_POS, F>(g, batch, st); return; \
-        case EPI_BIAS_RESID: launch_256<EPI_BIAS_RESID, F>(g, batch, st); return;  \
-        case EPI_KVSPLIT: launch_256<EPI_KVSPLIT, F>(g, batch, st); return;        \
-        case EPI_BIAS_SWISH: launch_256<EPI_BIAS_SWISH, F>(g, batch, st); return;  \
-        case EPI_BIAS_RELU: launch_256<EPI_BIAS_RELU, F>(g, batch, st); return;    \
-        case EPI_BIAS_F32: launch_256<EPI_BIAS_F32, F>(g, batch, st); return;      \
-        case EPI_PARTIAL: launch_256<EPI_PARTIAL, F>(g, batch, st); return;        \
-    }
-#define SPT_GEMM_SKINNY_CASES(F)                                                   \
-    switch (epi) {                                                                 \
-        case EPI_BIAS: launch_skinny<EPI_BIAS, F>(g, st); return;                  \
-        case EPI_BIAS_GELU: launch_skinny<EPI_BIAS_GELU, F>(g, st); return;        \
-        case EPI_BIAS_RESID: launch_skinny<EPI_BIAS_RESID, F>(g, st); return;      \
-        case EPI_BIAS_SWISH: launch_skinny<EPI_BIAS_SWISH, F>(g, st); return;      \
-        case EPI_BIAS_RELU: launch_skinny<EPI_BIAS_RELU, F>(g, st); return;        \
-        case EPI_BIAS_F32: launch_skinny<EPI_BIAS_F32, F>(g, st); return;          \
-        case EPI_PARTIAL: launch_skinny<EPI_PARTIAL, F>(g, st); return;            \
-    }
+    if (epi < EPI_BIAS || epi > EPI_PARTIAL) throw std::runtime_error("gemm_nt: bad epilogue");
+    // every kernel stages A and W in 16-byte pieces (global_load_lds_dwordx4; the skinny kernel's
+    // fragment loads): a row, a batch item or a base off that grid would fault or read another element
+    if (misaligned16(g.A) || misaligned16(g.W) || misaligned16(g.lda, esz) || misaligned16(g.ldw, esz) ||
+        (batch > 1 && misaligned16(g.sA, esz)))
+        throw std::runtime_error("gemm_nt: A, W, lda, ldw and the batch stride of A must be 16-byte aligned");
     if (variant == 3) {  // skinny (M <= 64): bf16 / f16, N % 16, K / ksplit % 128
-        if (dtype == DT_F32 || g.M > 64 || g.N % 16 || (g.K / g.ksplit) % 128)
+        if (dtype == DT_F32 || g.M <= 0 || g.M > 64 || g.N % 16 || (g.K / g.ksplit) % 128)
             throw std::runtime_error("gemm_nt: skinny variant needs a 16-bit dtype, M <= 64, N % 16, (K / ksplit) % 128");
-        if (dtype == DT_F16) { SPT_GEMM_SKINNY_CASES(true) }
-        else { SPT_GEMM_SKINNY_CASES(false) }
-        throw std::runtime_error("gemm_nt: bad epilogue for the skinny variant");
+        // launch_skinny has no grid z and the kernel reads neither sA nor sC
+        if (batch != 1) throw std::runtime_error("gemm_nt: skinny variant takes batch == 1 only");
+        if (epi == EPI_BIAS_GELU_POS || epi == EPI_KVSPLIT)
+            throw std::runtime_error("gemm_nt: bad epilogue for the skinny variant");
+        return 3;
     }
-#undef SPT_GEMM_SKINNY_CASES
     static const bool force128 = getenv("SPT_GEMM128") != nullptr;  // A/B switch for measurements
     // f32 (Whisper-small C2: one 30 s window gives 72-288 128 x 128 tiles on 256 CUs) takes the 64-row
     // tiles, like the 16-bit types (r6, profiles/r6/exp_f32_small_tiles.txt: C2 encoder 7.11 -> 5.42 ms);
@@ -845,6 +826,63 @@ void gemm_nt_variant(int dtype, int epi, const GemmArgs& g, int batch, int varia
     const bool use256 = variant == 2 || (variant == 0 && !force128);
     const bool fits32 = (int64_t)g.M * g.lda < (1ll << 31) && (int64_t)g.N * g.ldw < (1ll << 31);
     if (dtype != DT_F32 && use256 && fits32 && g.N % G2_BN == 0 && (g.K / g.ksplit) % 64 == 0) {
+        // the 256 x 256 epilogue loads and stores C (and reads pos) as 16-byte vectors
+        const bool f32out = epi == EPI_BIAS_RESID || epi == EPI_BIAS_GELU_POS || epi == EPI_BIAS_F32 || epi == EPI_PARTIAL;
+        const int osz = f32out ? 4 : 2;
+        bool bad = misaligned16(g.C);
+        if (epi == EPI_PARTIAL) bad = bad || misaligned16(g.ldc, osz) || (g.ksplit > 1 && misaligned16(g.c_split, osz));
+        else if (epi != EPI_KVSPLIT) bad = bad || misaligned16(g.ldc, osz) || (batch > 1 && misaligned16(g.sC, osz));
+        if (epi == EPI_BIAS_GELU_POS) bad = bad || misaligned16(g.pos);
+        if (bad)
+            throw std::runtime_error("gemm_nt: the 256 x 256 tile needs C, ldc, the batch / slab stride of C and pos 16-byte aligned");
+        return 2;
+    }
+    return variant == 4 || variant == 5 ? variant : 1;
+}
+
+void gemm_nt_variant(int dtype, int epi, const GemmArgs& g, int batch, int variant, hipStream_t st) {
+    const int kernel = gemm_nt_plan(dtype, epi, g, batch, variant);
+#define SPT_GEMM_CASES(T)                                                          \
+    switch (epi) {                                                                 \
+        case EPI_BIAS: launch_t<T, EPI_BIAS>(g, batch, kernel, st); return;       \
+        case EPI_BIAS_GELU: launch_t<T, EPI_BIAS_GELU>(g, batch, kernel, st); return; \
+        case EPI_BIAS_GELU_POS: launch_t<T, EPI_BIAS_GELU_POS>(g, batch, kernel, st); return; \
+        case EPI_BIAS_RESID: launch_t<T, EPI_BIAS_RESID>(g, batch, kernel, st); return; \
+        case EPI_KVSPLIT: launch_t<T, EPI_KVSPLIT>(g, batch, kernel, st); return; \
+        case EPI_BIAS_SWISH: launch_t<T, EPI_BIAS_SWISH>(g, batch, kernel, st); return; \
+        case EPI_BIAS_RELU: launch_t<T, EPI_BIAS_RELU>(g, batch, kernel, st); return; \
+        case EPI_BIAS_F32: launch_t<T, EPI_BIAS_F32>(g, batch, kernel, st); return; \
+        case EPI_PARTIAL: launch_t<T, EPI_PARTIAL>(g, batch, kernel, st); return; \
+    }
+#define SPT_GEMM256_CASES(F)                                                       \
+    switch (epi) {                                                                 \
+        case EPI_BIAS: launch_256<EPI_BIAS, F>(g, batch, st); return;              \
+        case EPI_BIAS_GELU: launch_256<EPI_BIAS_GELU, F>(g, batch, st); return;    \
+        case EPI_BIAS_GELU_POS: launch_256<EPI_BIAS_GELU_POS, F>(g, batch, st); return; \
+        case EPI_BIAS_RESID: launch_256<EPI_BIAS_RESID, F>(g, batch, st); return;  \
+        case EPI_KVSPLIT: launch_256<EPI_KVSPLIT, F>(g, batch, st); return;        \
+        case EPI_BIAS_SWISH: launch_256<EPI_BIAS_SWISH, F>(g, batch, st); return;  \
+        case EPI_BIAS_RELU: launch_256<EPI_BIAS_RELU, F>(g, batch, st); return;    \
+        case EPI_BIAS_F32: launch_256<EPI_BIAS_F32, F>(g, batch, st); return;      \
+        case EPI_PARTIAL: launch_256<EPI_PARTIAL, F>(g, batch, st); return;        \
+    }
+#define SPT_GEMM_SKINNY_CASES(F)                                                   \
+    switch (epi) {                                                                 \
+        case EPI_BIAS: launch_skinny<EPI_BIAS, F>(g, st); return;                  \
+        case EPI_BIAS_GELU: launch_skinny<EPI_BIAS_GELU, F>(g, st); return;        \
+        case EPI_BIAS_RESID: launch_skinny<EPI_BIAS_RESID, F>(g, st); return;      \
+        case EPI_BIAS_SWISH: launch_skinny<EPI_BIAS_SWISH, F>(g, st); return;      \
+        case EPI_BIAS_RELU: launch_skinny<EPI_BIAS_RELU, F>(g, st); return;        \
+        case EPI_BIAS_F32: launch_skinny<EPI_BIAS_F32, F>(g, st); return;          \
+        case EPI_PARTIAL: launch_skinny<EPI_PARTIAL, F>(g, st); return;            \
+    }
+    if (kernel == 3) {
+        if (dtype == DT_F16) { SPT_GEMM_SKINNY_CASES(true) }
+        else { SPT_GEMM_SKINNY_CASES(false) }
+        throw std::runtime_error("gemm_nt: bad epilogue for the skinny variant");
+    }
+#undef SPT_GEMM_SKINNY_CASES
+    if (kernel == 2) {
         if (dtype == DT_F16) { SPT_GEMM256_CASES(true) }
         else { SPT_GEMM256_CASES(false) }
     }

@@ -10,6 +10,15 @@ namespace spt {
 
 namespace {
 
+// The squared deviations of one float4, spelled out so that every instantiation rounds them alike.
+// Left to the compiler, (a * a + b * b) + (c * c + e * e) became two rounded squares and two fused ones
+// everywhere but in the float and f16 instances for d <= 256, which summed four rounded squares: a
+// variance off in the last bit, and layernorm_pend2 (bf16) off layernorm_pend (f32) + layernorm.
+__device__ __forceinline__ float sq_dev4(float a, float b, float c, float e) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(a, a, b * b) + __builtin_fmaf(c, c, e * e);
+}
+
 template <typename T> __device__ __forceinline__ void store4(T* p, float a, float b, float c, float d);
 template <> __device__ __forceinline__ void store4<float>(float* p, float a, float b, float c, float d) {
     *(float4*)p = make_float4(a, b, c, d);
@@ -52,7 +61,7 @@ __global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x, in
     for (int i = 0; i < NV; ++i) {
         if (lane + 64 * i < n4) {
             const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, e = v[i].w - mean;
-            s2 += (a * a + b * b) + (c * c + e * e);
+            s2 += sq_dev4(a, b, c, e);
         }
     }
     const float rstd = 1.0f / sqrtf(wave_sum(s2) / (float)d + 1e-5f);
@@ -149,7 +158,7 @@ __global__ __launch_bounds__(256) void ln_pend_kernel(float* __restrict__ x, int
         const int idx = lane + 64 * i;
         if (idx < n4) {
             const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, e = v[i].w - mean;
-            s2 += (a * a + b * b) + (c * c + e * e);
+            s2 += sq_dev4(a, b, c, e);
         }
     }
     const float rstd = 1.0f / sqrtf(wave_sum(s2) / (float)d + 1e-5f);
@@ -214,7 +223,7 @@ __global__ __launch_bounds__(256) void ln_pend2_kernel(const float* __restrict__
     for (int i = 0; i < NV; ++i) {
         if (lane + 64 * i < n4) {
             const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, e = v[i].w - mean;
-            s2 += (a * a + b * b) + (c * c + e * e);
+            s2 += sq_dev4(a, b, c, e);
         }
     }
     float rstd = 1.0f / sqrtf(wave_sum(s2) / (float)d + 1e-5f);
@@ -238,7 +247,7 @@ __global__ __launch_bounds__(256) void ln_pend2_kernel(const float* __restrict__
     for (int i = 0; i < NV; ++i) {
         if (lane + 64 * i < n4) {
             const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, e = v[i].w - mean;
-            s2 += (a * a + b * b) + (c * c + e * e);
+            s2 += sq_dev4(a, b, c, e);
         }
     }
     rstd = 1.0f / sqrtf(wave_sum(s2) / (float)d + 1e-5f);
@@ -339,6 +348,7 @@ void layernorm_pend(int dtype, float* x, int M, int d, const float* slab, int ks
                     const float* pbias, float alpha, const float* w, const float* b, void* y, bool write_x,
                     hipStream_t st) {
     if (d % 4) throw std::runtime_error("layernorm_pend: d % 4");
+    if (!pbias) throw std::runtime_error("layernorm_pend: null pbias (the kernel reads it unconditionally)");
     if (dtype == DT_BF16) ln_pend_dispatch<bf16>(x, M, d, slab, ks, slab_stride, pbias, alpha, w, b, (bf16*)y, write_x, st);
     else if (dtype == DT_F16) ln_pend_dispatch<f16>(x, M, d, slab, ks, slab_stride, pbias, alpha, w, b, (f16*)y, write_x, st);
     else ln_pend_dispatch<float>(x, M, d, slab, ks, slab_stride, pbias, alpha, w, b, (float*)y, write_x, st);
@@ -349,6 +359,7 @@ void layernorm_pend2(int dtype2, const float* x, int M, int d, const float* slab
                      const float* pbias, float alpha, const float* w, const float* b, float* y, const float* w2,
                      const float* b2, void* y2, hipStream_t st) {
     if (d % 4) throw std::runtime_error("layernorm_pend2: d % 4");
+    if (!pbias) throw std::runtime_error("layernorm_pend2: null pbias (the kernel reads it unconditionally)");
     if (dtype2 == DT_BF16) ln_pend2_dispatch<bf16>(x, M, d, slab, ks, slab_stride, pbias, alpha, w, b, y, w2, b2, (bf16*)y2, st);
     else if (dtype2 == DT_F16) ln_pend2_dispatch<f16>(x, M, d, slab, ks, slab_stride, pbias, alpha, w, b, y, w2, b2, (f16*)y2, st);
     else ln_pend2_dispatch<float>(x, M, d, slab, ks, slab_stride, pbias, alpha, w, b, y, w2, b2, (float*)y2, st);

@@ -53,6 +53,11 @@ void gemm_nt(int dtype, int epi, const GemmArgs& g, int batch, hipStream_t st);
 // constructors call it before any stream capture; launches check it too)
 void gemm_prepare();
 void gemm_nt_variant(int dtype, int epi, const GemmArgs& g, int batch, int variant, hipStream_t st);
+// what gemm_nt_variant checks before it launches, alone: throws on everything the launcher refuses (a
+// shape, a split, an epilogue the variant lacks, batch != 1 on the skinny variant, an operand off the
+// 16-byte grid its kernel loads or stores on) and returns the kernel that runs (1: 128 x 128,
+// 2: 256 x 256, 3: skinny, 4: 64 x 128, 5: 64 x 64).  Host only; reads no memory.
+int gemm_nt_plan(int dtype, int epi, const GemmArgs& g, int batch, int variant);
 
 // ------------------------------------------------------------------ weights (k_init.hip)
 enum { WK_MAT = 0, WK_BIAS = 1, WK_LNW = 2, WK_LNB = 3, WK_TOK = 4, WK_DPOS = 5 };
