@@ -551,6 +551,90 @@ spt_status spt_debug_qgemv(int32_t device, int32_t dtype, int32_t ggml_type, con
                            float* out_plain, float* out_packed, float* top_plain, float* top_packed, float* unpacked,
                            char* err, size_t errlen);
 
+/* The decoder GEMV and the small kernels of the decode step alone (additive over ABI 14, announced by
+ * SPT_HAS_GEMV_KERNELS), under the rules of the hooks above: no context, a stream and
+ * buffers of the call's own on `device`, host f32 in and out, every refusal made on the host before
+ * any launch (SPT_ERR_INVALID_ARG with the reason in err), a valid call without a device
+ * SPT_ERR_DEVICE.  Every buffer a kernel writes starts with each byte 0xFF (a NaN in f32, bf16 and
+ * f16; -1 in an int) and comes back whole, so what a launch did not write is the caller's to inspect.
+ *
+ * spt_debug_gemv: one gemv() launch on dense weights W [N][K], given as f32 and rounded to dtype
+ * (SPT_DTYPE_F32, _BF16 or _F16) on the host.  R in 1..64.  (mode, a_src) is one of the decoder's pairs.
+ *   a_src  SPT_GEMV_A_DIRECT: A [a_count] rounded to dtype, row i at A + i * lda + a_row0.
+ *          SPT_GEMV_A_LN: A [a_count] the f32 residual rows in the same layout; pend [n_pend][a_count]
+ *            the pending slabs in A's layout (n_pend 0, 1, 2 or 4; the unused ones are a zero slab);
+ *            ln_w, ln_b [K]; x_out (optional) [a_count]: the summed rows as workgroup (0, 0) writes them.
+ *          SPT_GEMV_A_ATTN: apart [R][H][S][66] = {o[64], m, l}, S in {2, 3, 4, 8}, H * 64 == K.  With
+ *            merge_first (S = 8) the call also runs dec_attn_part_merge and the SPT_GEMV_A_DIRECT
+ *            projection of its output on the same operands: that second C comes back in out_merged.
+ *   C      [c_count] with row i at C + i * ldc (ldc >= N).  SPT_GV_BIAS_RESID: in (the f32 rows the
+ *          product is added to) and out; every other mode: out only.  SPT_GV_PARTIAL: slab s at
+ *          C + s * c_split, p_resid (optional) [R][ldc] added into slab 0.  SPT_GV_QKV_CACHE (N = 3 d,
+ *          d = 64 cache_H, R = B * Tq): q in columns 0..d-1 of C, k and v into cache
+ *          [2][B][cache_H][ctx][64] at positions pos0 .. pos0 + Tq - 1 (pos0 + Tq <= ctx).
+ *          SPT_GV_LOGITS: the f32 logits; suppress [suppress_words >= ceil(N / 32)] the mask, blank0 /
+ *          blank1 the columns also suppressed while step == 0, part [R][n_tiles][4] the top-2 partials as
+ *          stored (f32 best, i32 index, f32 runner-up, 0).
+ *   plan   (optional) int32 [8]: what gemv_plan() chose: waves, column tiles, super-steps in flight,
+ *          exact, row groups, LDS bytes, grid x, grid y.  Written before the device is looked for. */
+#define SPT_HAS_GEMV_KERNELS 1
+enum { SPT_GEMV_A_DIRECT = 0, SPT_GEMV_A_LN = 1, SPT_GEMV_A_ATTN = 2 };
+typedef struct spt_gemv_debug {
+    const float* W;
+    const float* A;
+    const float* ln_w;
+    const float* ln_b;
+    const float* pend;
+    float* x_out;
+    const float* apart;
+    float* out_merged;
+    const float* bias;
+    float* C;
+    const float* p_resid;
+    float* cache;
+    const uint32_t* suppress;
+    float* part;
+    int32_t* plan;
+    int64_t a_count, c_count, c_split, suppress_words;
+    int32_t dtype, mode, a_src, R, N, K, lda, a_row0, n_pend, S, H, merge_first, ldc, ksplit;
+    int32_t B, Tq, cache_H, ctx, pos0, blank0, blank1, step, n_tiles, reserved0;
+} spt_gemv_debug;
+spt_status spt_debug_gemv(int32_t device, const spt_gemv_debug* args, char* err, size_t errlen);
+
+/* spt_debug_dec_step: the small kernels of the step.
+ *   SPT_DEC_STEP_EMBED     dec_embed: x [B * Tq][d] = emb[tok[r]] + pos[pos0 + r % Tq] (tok [B * Tq] in
+ *                          0..n_vocab-1, pos0 + Tq <= ctx); the state is not changed.
+ *   SPT_DEC_STEP_FINALIZE  dec_finalize n_steps times, step s on part [n_steps][B][n_tiles][4] (the
+ *                          partials as spt_debug_gemv returns them): next_tok [n_steps][B] and
+ *                          x [n_steps][B][d] per step; out_tok, out_top1, out_top2 [B][out_cap], done [B]
+ *                          (in and out) and the state after the last step.  forced [B][forced_len] or
+ *                          NULL.  state[0] + n_steps * Tq may pass ctx (the position row is clamped).
+ *   SPT_DEC_STEP_ADVANCE   dec_advance by n_advance; SPT_DEC_STEP_RESET  dec_reset.
+ *   emb    [n_vocab][d] f32 rounded to dtype on the host, or, with emb_q one of SPT_GGML_Q4_1 / _Q5_0 /
+ *          _Q5_1 (16-bit dtypes, d a multiple of 128), emb_blocks: the ggml blocks of [n_vocab][d / 32],
+ *          packed as spt_debug_qgemv packs W.  pos [ctx][d] f32.
+ *   state  int32 [4] in and out: pos0, step, epoch, arrive. */
+enum { SPT_DEC_STEP_EMBED = 0, SPT_DEC_STEP_FINALIZE = 1, SPT_DEC_STEP_ADVANCE = 2, SPT_DEC_STEP_RESET = 3 };
+typedef struct spt_dec_step_debug {
+    const int32_t* tok;
+    const float* part;
+    const int32_t* forced;
+    int32_t* done;
+    const float* emb;
+    const void* emb_blocks;
+    const float* pos;
+    int32_t* state;
+    int32_t* next_tok;
+    float* x;
+    int32_t* out_tok;
+    float* out_top1;
+    float* out_top2;
+    size_t emb_blocks_bytes;
+    int32_t dtype, op, B, Tq, d, ctx, n_vocab, n_tiles, n_steps, forced_len, ignore_eot, out_cap, eot, emb_q;
+    int32_t n_advance, reserved0;
+} spt_dec_step_debug;
+spt_status spt_debug_dec_step(int32_t device, const spt_dec_step_debug* args, char* err, size_t errlen);
+
 /* ================================================================================================
  * ABI 6: Parakeet-V3 (NeMo FastConformer-TDT), the app's other local engine;
  * ABI 8: spt_parakeet_create takes the app's model directory (the int8 ONNX export) natively.

@@ -43,6 +43,14 @@ pub const SPT_GV_LOGITS: i32 = 4;
 pub const SPT_GV_BIAS_RESID: i32 = 5;
 pub const SPT_QGEMV_A_DIRECT: i32 = 0;
 pub const SPT_QGEMV_A_LN: i32 = 1;
+/// `a_src` of `spt_gemv_debug` and `op` of `spt_dec_step_debug` (SPT_HAS_GEMV_KERNELS)
+pub const SPT_GEMV_A_DIRECT: i32 = 0;
+pub const SPT_GEMV_A_LN: i32 = 1;
+pub const SPT_GEMV_A_ATTN: i32 = 2;
+pub const SPT_DEC_STEP_EMBED: i32 = 0;
+pub const SPT_DEC_STEP_FINALIZE: i32 = 1;
+pub const SPT_DEC_STEP_ADVANCE: i32 = 2;
+pub const SPT_DEC_STEP_RESET: i32 = 3;
 /// `spt_pk_act` of `spt_parakeet_debug_qgemm`
 pub const SPT_PK_ACT_NONE: i32 = 0;
 pub const SPT_PK_ACT_RELU: i32 = 1;
@@ -56,6 +64,93 @@ pub const SPT_SUPPRESS_NST: u32 = 8;
 pub const SPT_MODEL_WEIGHTS_EXTERNAL: u32 = 1;
 /// quantised decoder matrices of a ggml file stay resident in their blocks (SPT_HAS_QUANT_RESIDENT)
 pub const SPT_MODEL_QUANT_RESIDENT: u32 = 2;
+
+/// the arguments of `spt_debug_gemv` (one decoder GEMV launch on caller-supplied arrays)
+#[repr(C)]
+#[allow(non_snake_case)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_gemv_debug {
+    pub W: *const f32,
+    pub A: *const f32,
+    pub ln_w: *const f32,
+    pub ln_b: *const f32,
+    pub pend: *const f32,
+    pub x_out: *mut f32,
+    pub apart: *const f32,
+    pub out_merged: *mut f32,
+    pub bias: *const f32,
+    pub C: *mut f32,
+    pub p_resid: *const f32,
+    pub cache: *mut f32,
+    pub suppress: *const u32,
+    pub part: *mut f32,
+    pub plan: *mut i32,
+    pub a_count: i64,
+    pub c_count: i64,
+    pub c_split: i64,
+    pub suppress_words: i64,
+    pub dtype: i32,
+    pub mode: i32,
+    pub a_src: i32,
+    pub R: i32,
+    pub N: i32,
+    pub K: i32,
+    pub lda: i32,
+    pub a_row0: i32,
+    pub n_pend: i32,
+    pub S: i32,
+    pub H: i32,
+    pub merge_first: i32,
+    pub ldc: i32,
+    pub ksplit: i32,
+    pub B: i32,
+    pub Tq: i32,
+    pub cache_H: i32,
+    pub ctx: i32,
+    pub pos0: i32,
+    pub blank0: i32,
+    pub blank1: i32,
+    pub step: i32,
+    pub n_tiles: i32,
+    pub reserved0: i32,
+}
+
+/// the arguments of `spt_debug_dec_step` (dec_embed / dec_finalize / dec_advance / dec_reset alone)
+#[repr(C)]
+#[allow(non_snake_case)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_dec_step_debug {
+    pub tok: *const i32,
+    pub part: *const f32,
+    pub forced: *const i32,
+    pub done: *mut i32,
+    pub emb: *const f32,
+    pub emb_blocks: *const c_void,
+    pub pos: *const f32,
+    pub state: *mut i32,
+    pub next_tok: *mut i32,
+    pub x: *mut f32,
+    pub out_tok: *mut i32,
+    pub out_top1: *mut f32,
+    pub out_top2: *mut f32,
+    pub emb_blocks_bytes: usize,
+    pub dtype: i32,
+    pub op: i32,
+    pub B: i32,
+    pub Tq: i32,
+    pub d: i32,
+    pub ctx: i32,
+    pub n_vocab: i32,
+    pub n_tiles: i32,
+    pub n_steps: i32,
+    pub forced_len: i32,
+    pub ignore_eot: i32,
+    pub out_cap: i32,
+    pub eot: i32,
+    pub emb_q: i32,
+    pub n_advance: i32,
+    pub reserved0: i32,
+}
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
@@ -626,6 +721,15 @@ extern "C" {
         top_plain: *mut f32,
         top_packed: *mut f32,
         unpacked: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+
+    // the decoder GEMV and the step's small kernels alone (SPT_HAS_GEMV_KERNELS)
+    pub fn spt_debug_gemv(device: i32, args: *const spt_gemv_debug, err: *mut c_char, errlen: usize) -> spt_status;
+    pub fn spt_debug_dec_step(
+        device: i32,
+        args: *const spt_dec_step_debug,
         err: *mut c_char,
         errlen: usize,
     ) -> spt_status;

@@ -65,6 +65,8 @@ EXPORTS = [
     "spt_debug_gemm", "spt_debug_layernorm",
     # quantised decoder weights resident in HBM (SPT_HAS_QUANT_RESIDENT)
     "spt_debug_qgemv", "spt_get_weight_residency",
+    # the decoder GEMV and the step's small kernels alone (SPT_HAS_GEMV_KERNELS)
+    "spt_debug_gemv", "spt_debug_dec_step",
     # the token-alignment kernels alone (SPT_HAS_ALIGN_KERNELS)
     "spt_debug_align_qk", "spt_debug_align_norm", "spt_debug_align_dtw", "spt_debug_align_words",
     # DTW token and word timestamps (SPT_HAS_TOKEN_TIMESTAMPS)
@@ -90,6 +92,8 @@ SPT_MODEL_QUANT_RESIDENT = 2
 SPT_GGML_Q4_1, SPT_GGML_Q5_0, SPT_GGML_Q5_1 = 3, 6, 7
 SPT_GV_BIAS, SPT_GV_BIAS_GELU, SPT_GV_PARTIAL, SPT_GV_QKV_CACHE, SPT_GV_LOGITS, SPT_GV_BIAS_RESID = range(6)
 SPT_QGEMV_A_DIRECT, SPT_QGEMV_A_LN = 0, 1
+SPT_GEMV_A_DIRECT, SPT_GEMV_A_LN, SPT_GEMV_A_ATTN = 0, 1, 2
+SPT_DEC_STEP_EMBED, SPT_DEC_STEP_FINALIZE, SPT_DEC_STEP_ADVANCE, SPT_DEC_STEP_RESET = range(4)
 SPT_ATTN_CROSS_8WAVE, SPT_ATTN_CROSS_VW, SPT_ATTN_CROSS_VW_PQ, SPT_ATTN_CROSS_VW_MERGE, SPT_ATTN_CROSS_VW_PQ_MERGE = range(5)
 SPT_LN_PLAIN, SPT_LN_PEND, SPT_LN_PEND2 = range(3)
 SPT_SV_LANG_AUTO, SPT_SV_LANG_ZH, SPT_SV_LANG_EN, SPT_SV_LANG_YUE, SPT_SV_LANG_JA, SPT_SV_LANG_KO = range(6)
@@ -100,6 +104,30 @@ SPT_MODEL_WEIGHTS_EXTERNAL = 1
 PK_STAGES = ("subsampling", "pos", "layernorm", "ffn", "qkv_out", "attn", "conv_pw", "conv_dw", "joint_enc")
 PROBES = {"dec_cross_attn": 0, "dec_self_attn": 1, "dec_logits": 2, "dec_fc1": 3, "enc_fc1_gemm": 4,
           "enc_attn": 5}
+
+
+_FP, _I32P = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+
+
+class GemvDebug(C.Structure):
+    """spt_gemv_debug"""
+    _fields_ = [(n, _FP) for n in ("W", "A", "ln_w", "ln_b", "pend", "x_out", "apart", "out_merged", "bias", "C",
+                                   "p_resid", "cache")] + \
+               [("suppress", C.POINTER(C.c_uint32)), ("part", _FP), ("plan", _I32P)] + \
+               [(n, C.c_int64) for n in ("a_count", "c_count", "c_split", "suppress_words")] + \
+               [(n, C.c_int32) for n in ("dtype", "mode", "a_src", "R", "N", "K", "lda", "a_row0", "n_pend", "S", "H",
+                                         "merge_first", "ldc", "ksplit", "B", "Tq", "cache_H", "ctx", "pos0", "blank0",
+                                         "blank1", "step", "n_tiles", "reserved0")]
+
+
+class DecStepDebug(C.Structure):
+    """spt_dec_step_debug"""
+    _fields_ = [("tok", _I32P), ("part", _FP), ("forced", _I32P), ("done", _I32P), ("emb", _FP),
+                ("emb_blocks", C.c_void_p), ("pos", _FP), ("state", _I32P), ("next_tok", _I32P), ("x", _FP),
+                ("out_tok", _I32P), ("out_top1", _FP), ("out_top2", _FP), ("emb_blocks_bytes", C.c_size_t)] + \
+               [(n, C.c_int32) for n in ("dtype", "op", "B", "Tq", "d", "ctx", "n_vocab", "n_tiles", "n_steps",
+                                         "forced_len", "ignore_eot", "out_cap", "eot", "emb_q", "n_advance",
+                                         "reserved0")]
 
 
 class ModelParams(C.Structure):
@@ -466,6 +494,9 @@ def load():
     L.spt_debug_qgemv.argtypes = [i32, i32, i32, C.c_void_p, C.c_size_t, i32, i32, fp, i32, fp, fp, fp, fp, i32, i32,
                                   i32, fp, fp, fp, fp, fp, C.c_char_p, C.c_size_t]
     L.spt_debug_qgemv.restype = C.c_int
+    L.spt_debug_gemv.argtypes = [i32, C.POINTER(GemvDebug), C.c_char_p, C.c_size_t]
+    L.spt_debug_dec_step.argtypes = [i32, C.POINTER(DecStepDebug), C.c_char_p, C.c_size_t]
+    L.spt_debug_gemv.restype = L.spt_debug_dec_step.restype = C.c_int
     L.spt_get_weight_residency.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.spt_get_weight_residency.restype = C.c_int
     # the token-alignment kernels alone

@@ -601,63 +601,90 @@ void gemv_attr_modes() {
 #undef SPT_PAIR
 }
 
-template <typename T, int MODE, int ASRC, int RG>
-void gemv_launch_rg(const GemvArgs& a, hipStream_t st) {
-    const int nss = cdiv(a.K / GV<T>::KS, a.ksplit);  // super-steps per workgroup
-    if constexpr (MODE == GV_LOGITS) {
+// The geometry of one launch (host only): waves, column tiles per workgroup, super-steps in flight per
+// wave, whether every wave's K slice is exact, the row groups and the dynamic LDS.  esz: the dtype's
+// element size (KS = 128 / 64); code: the kernel-side A source; nss = super-steps of K per workgroup.
+// Throws where no configuration holds the K slice.  gemv_launch_rg launches what this returns, and
+// gemv_plan() (kernels.h) returns it to callers that only ask.
+inline GemvPlan gemv_shape(int esz, int mode, int code, int R, int N, int K, int ksplit) {
+    GemvPlan p{};
+    p.code = code;
+    p.rg = R <= 16 ? 1 : R <= 32 ? 2 : 4;
+    auto cfg = [&](int nwv, int ct, int maxj, bool exact) {
+        p.nwv = nwv; p.ct = ct; p.maxj = maxj; p.exact = exact;
+        const int red = nwv * p.rg * 64 * (int)sizeof(f32x4);
+        p.lds_bytes = (code != A_DIRECT ? gv_img_bytes(R, K, esz) : 0) + (nwv / ct > 1 ? red : 0);
+        p.grid_x = cdiv(N, 16 * ct);
+        p.grid_y = ksplit;
+        return p;
+    };
+    const int nss = cdiv(K / (esz == 2 ? 128 : 64), ksplit);  // super-steps per workgroup
+    if (mode == GV_LOGITS) {
         // one wave per 16-column tile over all of K either way (bitwise the same logits); wider
         // workgroups stage each LayerNorm image for more tiles (SPT_GV_LOGITS_CT = 4 / 8, r4)
         static const int lct = getenv("SPT_GV_LOGITS_CT") ? atoi(getenv("SPT_GV_LOGITS_CT")) : 4;
-        if (lct == 8) gemv_launch_cfg<T, MODE, ASRC, RG, 8, 8, 4>(a, st);
-        else gemv_launch_cfg<T, MODE, ASRC, RG, 4, 4, 4>(a, st);
+        return lct == 8 ? cfg(8, 8, 4, false) : cfg(4, 4, 4, false);
+    }
+    // Wide LayerNorm-prologue GEMVs (fc1, N = 4d >= 4096): two column tiles per workgroup,
+    // so half as many workgroups re-read the residual rows for their LayerNorm image (r1
+    // exp23: fc1 9.4 -> 8.6 us, RTFx +1.2 %; the QKV and cross-Q projections lose with it)
+    // an attention-merge prologue (A_ATTN) takes A_DIRECT's geometry: the same waves and K
+    // slices, so the cross output projection of merged key partials is bitwise the projection
+    // of the 8-wave kernel's output (dec_cross_attn_vw)
+    if (is_ln(code)) {
+        // K = 10 super-steps (large-v3's d = 1280 in bf16): 10 waves, each an exact slice, so
+        // the LayerNorm does not wait for the weight stream (GV_EXACT_LN=0 restores r1's shapes)
+        static const bool exact_ln = !getenv("GV_EXACT_LN") || atoi(getenv("GV_EXACT_LN")) != 0;
+        // SPT_GV_CT2_MIN: the smallest N given two column tiles per workgroup (experiments)
+        static const int ct2_min = getenv("SPT_GV_CT2_MIN") ? atoi(getenv("SPT_GV_CT2_MIN")) : 4096;
+        if (exact_ln && nss == 10) return N >= ct2_min ? cfg(10, 2, 2, true) : cfg(10, 1, 1, true);
+        // K = 12 super-steps (Whisper-small's d = 768 in f32, the C2 decoder): 12 waves, one exact
+        // super-step each (experiment; SPT_GV_EXACT12=0: the 8-wave shape)
+        static const bool exact12 = !getenv("SPT_GV_EXACT12") || atoi(getenv("SPT_GV_EXACT12")) != 0;
+        if (exact_ln && exact12 && nss == 12) return cfg(12, 1, 1, true);
+        if (N >= 4096 && nss <= 24) return cfg(8, 2, 3, false);
     } else {
-        // Wide LayerNorm-prologue GEMVs (fc1, N = 4d >= 4096): two column tiles per workgroup,
-        // so half as many workgroups re-read the residual rows for their LayerNorm image (r1
-        // exp23: fc1 9.4 -> 8.6 us, RTFx +1.2 %; the QKV and cross-Q projections lose with it)
-        // an attention-merge prologue (A_ATTN) takes A_DIRECT's geometry: the same waves and K
-        // slices, so the cross output projection of merged key partials is bitwise the projection
-        // of the 8-wave kernel's output (dec_cross_attn_vw)
-        if constexpr (is_ln(ASRC)) {
-            // K = 10 super-steps (large-v3's d = 1280 in bf16): 10 waves, each an exact slice, so
-            // the LayerNorm does not wait for the weight stream (GV_EXACT_LN=0 restores r1's shapes)
-            static const bool exact_ln = !getenv("GV_EXACT_LN") || atoi(getenv("GV_EXACT_LN")) != 0;
-            // SPT_GV_CT2_MIN: the smallest N given two column tiles per workgroup (experiments)
-            static const int ct2_min = getenv("SPT_GV_CT2_MIN") ? atoi(getenv("SPT_GV_CT2_MIN")) : 4096;
-            if (exact_ln && nss == 10) {
-                if (a.N >= ct2_min) gemv_launch_cfg<T, MODE, ASRC, RG, 10, 2, 2, true>(a, st);
-                else gemv_launch_cfg<T, MODE, ASRC, RG, 10, 1, 1, true>(a, st);
-                return;
-            }
-            // K = 12 super-steps (Whisper-small's d = 768 in f32, the C2 decoder): 12 waves, one exact
-            // super-step each (experiment; SPT_GV_EXACT12=0: the 8-wave shape)
-            static const bool exact12 = !getenv("SPT_GV_EXACT12") || atoi(getenv("SPT_GV_EXACT12")) != 0;
-            if (exact_ln && exact12 && nss == 12) {
-                gemv_launch_cfg<T, MODE, ASRC, RG, 12, 1, 1, true>(a, st);
-                return;
-            }
-            if (a.N >= 4096 && nss <= 24) {
-                gemv_launch_cfg<T, MODE, ASRC, RG, 8, 2, 3>(a, st);
-                return;
-            }
-        }
         // the directly-read / attention-merge GEMVs of 12 super-steps (C2's self-out and cross-out) on
         // the same exact 12-wave split (r6ac: pass 0.623 -> 0.618 ms; SPT_GV_EXACT12_DIRECT=0: 8 waves).
         // A_DIRECT and A_ATTN keep one geometry, so the merged-partials projection stays bitwise the
         // merge kernel's
         static const bool exact12_direct = !getenv("SPT_GV_EXACT12_DIRECT") || atoi(getenv("SPT_GV_EXACT12_DIRECT")) != 0;
-        if constexpr (!is_ln(ASRC)) {
-            if (exact12_direct && nss == 12) {
-                gemv_launch_cfg<T, MODE, ASRC, RG, 12, 1, 1, true>(a, st);
-                return;
-            }
-        }
-        if (nss <= 8) gemv_launch_cfg<T, MODE, ASRC, RG, 4, 1, 2>(a, st);
-        else if (nss <= 16) gemv_launch_cfg<T, MODE, ASRC, RG, 8, 1, 2>(a, st);
-        else if constexpr (!is_ln(ASRC)) {  // 16 waves: no room for a staged A image's registers
-            if (nss <= 48) gemv_launch_cfg<T, MODE, ASRC, RG, 16, 1, 3>(a, st);
-            else throw std::runtime_error("gemv: K too large");
-        } else throw std::runtime_error("gemv: K too large for a staged A operand");
+        if (exact12_direct && nss == 12) return cfg(12, 1, 1, true);
     }
+    if (nss <= 8) return cfg(4, 1, 2, false);
+    if (nss <= 16) return cfg(8, 1, 2, false);
+    // 16 waves: no room for a staged A image's registers
+    if (is_ln(code)) throw std::runtime_error("gemv: K too large for a staged A operand");
+    if (nss <= 48) return cfg(16, 1, 3, false);
+    throw std::runtime_error("gemv: K too large");
+}
+
+template <typename T, int MODE, int ASRC, int RG>
+void gemv_launch_rg(const GemvArgs& a, hipStream_t st) {
+    const GemvPlan p = gemv_shape((int)sizeof(T), MODE, ASRC, a.R, a.N, a.K, a.ksplit);
+    // the configurations gemv_shape gives this (mode, A source) class: no other is instantiated
+#define SPT_CFG(NWV, CT, MAXJ, EX)                                            \
+    if (p.nwv == NWV && p.ct == CT && p.maxj == MAXJ && p.exact == EX) {      \
+        gemv_launch_cfg<T, MODE, ASRC, RG, NWV, CT, MAXJ, EX>(a, st);         \
+        return;                                                               \
+    }
+    if constexpr (MODE == GV_LOGITS) {
+        SPT_CFG(4, 4, 4, false)
+        SPT_CFG(8, 8, 4, false)
+    } else {
+        if constexpr (is_ln(ASRC)) {
+            SPT_CFG(10, 2, 2, true)
+            SPT_CFG(10, 1, 1, true)
+            SPT_CFG(8, 2, 3, false)
+        } else {
+            SPT_CFG(16, 1, 3, false)
+        }
+        SPT_CFG(12, 1, 1, true)
+        SPT_CFG(4, 1, 2, false)
+        SPT_CFG(8, 1, 2, false)
+    }
+#undef SPT_CFG
+    throw std::runtime_error("gemv: no kernel of the planned geometry");
 }
 
 template <typename T, int MODE, int ASRC>

@@ -515,7 +515,7 @@ int gemv_max_image_rows(int dtype, int K) {
     return r;
 }
 
-void gemv(int dtype, int mode, int asrc, const GemvArgs& a_in, hipStream_t st) {
+GemvPlan gemv_plan(int dtype, int mode, int asrc, const GemvArgs& a_in) {
     if (a_in.R > 64 || a_in.R <= 0) throw std::runtime_error("gemv: rows must be in 1..64");
     const int ks = dtype_size(dtype) == 2 ? 128 : 64;
     if (a_in.K % ks) throw std::runtime_error("gemv: K alignment");
@@ -540,6 +540,19 @@ void gemv(int dtype, int mode, int asrc, const GemvArgs& a_in, hipStream_t st) {
     if (a.wq) {  // a matrix resident in its packed blocks: the same checks, geometry and body (k_dec_q.hip)
         QPackGeom qg;
         if (esz != 2 || !qpack_geom(a.wq, &qg)) throw std::runtime_error("gemv: no resident layout for this weight type / dtype");
+    }
+#define SPT_GV(M, S) \
+    if (mode == M && code == S) return gemv_shape(esz, mode, code, a.R, a.N, a.K, a.ksplit);
+    SPT_GV_PAIRS(SPT_GV)
+#undef SPT_GV
+    throw std::runtime_error("gemv: unsupported mode / A source");
+}
+
+void gemv(int dtype, int mode, int asrc, const GemvArgs& a_in, hipStream_t st) {
+    const int code = gemv_plan(dtype, mode, asrc, a_in).code;
+    GemvArgs a = a_in;
+    a.ksplit = std::max(1, a.ksplit);
+    if (a.wq) {
         gemv_q(dtype, mode, code, a, st);
         return;
     }

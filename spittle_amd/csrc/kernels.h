@@ -172,6 +172,19 @@ struct GemvArgs {
 };
 constexpr int kMaxPend = 4;
 void gemv(int dtype, int mode, int asrc, const GemvArgs& a, hipStream_t st);
+// what gemv() checks before it launches, alone: throws on everything the launcher refuses (rows, K
+// alignment, a K split without partial outputs or beyond the super-steps, an A image beyond the LDS
+// budget, a LayerNorm or attention-merge prologue without its operands, a (mode, A source) pair the
+// decoder does not use, a K no configuration holds) and returns the launch's geometry.  Host only: it
+// reads which pointers are null, never what they point to, and needs no device.
+struct GemvPlan {
+    int code;                  // kernel-side A source: A_DIRECT, 16 + pending slabs, 32 + key chunks
+    int rg, nwv, ct, maxj;     // row groups of 16, waves, column tiles per workgroup, super-steps in flight
+    bool exact;                // every wave's K slice is exactly maxj super-steps
+    int lds_bytes;             // dynamic LDS: the staged A image + the cross-wave reduction
+    int grid_x, grid_y;
+};
+GemvPlan gemv_plan(int dtype, int mode, int asrc, const GemvArgs& a);
 // one-time per-process kernel attributes (call before any stream capture)
 void gemv_prepare(int dtype);
 // k_dec_q.hip: the same kernels with the weights fetched from a packed quantised matrix (a.wq != 0).
