@@ -635,6 +635,136 @@ typedef struct spt_dec_step_debug {
 } spt_dec_step_debug;
 spt_status spt_debug_dec_step(int32_t device, const spt_dec_step_debug* args, char* err, size_t errlen);
 
+/* The Parakeet encoder kernels alone (additive over ABI 14, announced by SPT_HAS_PK_KERNELS; DESIGN.md
+ * 9.8), under the rules of the hooks above.  lens [B][4] = the frame counts T, T1, T2, T3 of each
+ * utterance, as the engine keeps them on the device; every entry >= 0.
+ *
+ * spt_debug_pk_conv: one launch, by mode (Fo = (F - 1) / 2 + 1 and To = (Tp - 1) / 2 + 1 are the hook's):
+ *   SPT_PK_CONV0    pk_conv0: x = mel [B][Tp][F] (f32, not rounded), w [C][9], bias [C]
+ *                   -> y [B][To][Fo][C]; frames >= min(lens[b][0], Tp) read as zero.
+ *   SPT_PK_DWCONV1 / _DWCONV2  pk_dwconv at stage 1 / 2: x [B][Tp][F][C] (dtype) -> y [B][To][Fo][C];
+ *                   frames >= min(lens[b][stage], Tp) read as zero.
+ *   SPT_PK_CONV_MODULE  pk_conv_module: x [B * Tp][2 C] (dtype; F is ignored), w [C][9], bias [C],
+ *                   bn_g / bn_b / bn_m / bn_v [C] -> y [B * Tp][C]; lens[b][3] <= Tp.
+ *   y [y_count]: y_count >= the elements the launch owns; the rest are guards nothing may write.
+ * spt_debug_pk_relpos: one pk_relpos launch -> pe [pe_count >= (2 Tp - 1) d] (d even).
+ * spt_debug_pk_rel_attn: one pk_rel_attn_variant launch.  qkv [B * Tp][3 d], d = H * dk; p [p_count]
+ *   with row r of utterance b at p + p_off + b * p_bstride + r * ldp (2 Tp - 1 rows of d elements;
+ *   p_bstride != 0 is f32 only); pu, pv [H][dk] (f32, not rounded); out [out_count >= B * Tp * d].
+ *   variant SPT_PK_ATTN_AUTO / _VALU / _MFMA (MFMA: f16 at dk 64 or 128).  lens[b][3] <= Tp: the
+ *   kernels index their score row and the position rows from it unguarded.  ldp, p_off and p_bstride
+ *   lie on the 16-byte grid of the kernels' vector loads. */
+#define SPT_HAS_PK_KERNELS 1
+enum { SPT_PK_CONV0 = 0, SPT_PK_DWCONV1 = 1, SPT_PK_DWCONV2 = 2, SPT_PK_CONV_MODULE = 3 };
+enum { SPT_PK_ATTN_AUTO = 0, SPT_PK_ATTN_VALU = 1, SPT_PK_ATTN_MFMA = 2 };
+typedef struct spt_pk_conv_debug {
+    const float* x;
+    const int32_t* lens;
+    const float* w;
+    const float* bias;
+    const float* bn_g;
+    const float* bn_b;
+    const float* bn_m;
+    const float* bn_v;
+    float* y;
+    int64_t y_count;
+    int32_t dtype, mode, B, Tp, F, C;
+} spt_pk_conv_debug;
+spt_status spt_debug_pk_conv(int32_t device, const spt_pk_conv_debug* args, char* err, size_t errlen);
+spt_status spt_debug_pk_relpos(int32_t device, int32_t dtype, int32_t Tp, int32_t d, float* pe, int64_t pe_count,
+                               char* err, size_t errlen);
+typedef struct spt_pk_attn_debug {
+    const float* qkv;
+    const float* p;
+    const float* pu;
+    const float* pv;
+    const int32_t* lens;
+    float* out;
+    int64_t p_count, p_off, p_bstride, out_count;
+    int32_t dtype, variant, B, Tp, H, dk, ldp, reserved0;
+} spt_pk_attn_debug;
+spt_status spt_debug_pk_rel_attn(int32_t device, const spt_pk_attn_debug* args, char* err, size_t errlen);
+
+/* spt_debug_pk_tdt: pk_state_init, then n_steps of pk_joint_fin, step s on the caller's partials
+ * part [n_steps][B][n_tiles][4] (f32 best, i32 index as stored, f32 runner-up, unused: what the joint stage
+ * writes per 64-output tile) and duration logits dur [n_steps][B][n_dur].  emb [V + 1][P], fe [B * T3p][P],
+ * lens [B][4] with 0 <= lens[b][3] <= T3p.  Returned for slot 0 (after pk_state_init) and slot s + 1 (after
+ * step s): state [n_steps + 1][B][7] = {t, at_t, n_out, done, upd, tok, t3p}, xemb and fecur
+ * [n_steps + 1][B][P]; per step the four output arrays whole, out_tok / out_frame (int32) and out_t1 /
+ * out_t2 [n_steps][B * cap + 1] (the last element is a guard nothing may write; every element starts as
+ * 0xFF bytes).  Refused: a partial whose best is NaN, a best above -inf whose index is outside 0 .. V, and
+ * a (step, row) with no best above -inf: the kernel reads the embedding row of the index it finds. */
+typedef struct spt_pk_tdt_debug {
+    const float* part;
+    const float* dur;
+    const int32_t* lens;
+    const float* emb;
+    const float* fe;
+    int32_t* state;
+    float* xemb;
+    float* fecur;
+    int32_t* out_tok;
+    int32_t* out_frame;
+    float* out_t1;
+    float* out_t2;
+    int32_t B, P, V, n_dur, n_tiles, n_steps, max_symbols, cap, T3p, reserved0;
+} spt_pk_tdt_debug;
+spt_status spt_debug_pk_tdt(int32_t device, const spt_pk_tdt_debug* args, char* err, size_t errlen);
+
+/* spt_debug_pk_dec_stage: one pk_decode_stage launch of the TDT step, by mode, on plain weights the hook
+ * places with pk_place_lstm / pk_place_blocked into a buffer of the padded size that starts as NaN bytes.
+ * P up to 640 and a multiple of 64 (LSTM), 128 (PRED) or 32 (JOINT): what pk_decode_stage admits; B in 1..64;
+ * state [B][7] are the PkState rows (the stages read upd).
+ *   SPT_PK_DEC_LSTM   W = W_ih, W2 = W_hh [4P][P] (gate rows i, f, g, o), b0 = b_ih, b1 = b_hh [4P],
+ *                     xin, h_in, c_in [B][P] -> h_out, c_out [B][P] (rows with upd = 0: h_in, c_in as given).
+ *   SPT_PK_DEC_PRED   W [P][P], b0 [P], xin [B][P] -> gp [B][P], in and out (rows with upd = 0 untouched).
+ *   SPT_PK_DEC_JOINT  W [N][P], b0 [N], N = V + 1 + n_dur; x = ReLU(fe + gp), fe and gp [B][P] ->
+ *                     part [B][n_tiles][4] (n_tiles = ceil(N / 64); f32 best, i32 index, f32 runner-up, 0 of
+ *                     the tile's outputs n <= V) and dur [B][n_dur]. */
+enum { SPT_PK_DEC_LSTM = 0, SPT_PK_DEC_PRED = 1, SPT_PK_DEC_JOINT = 2 };
+typedef struct spt_pk_dec_debug {
+    const float* W;
+    const float* W2;
+    const float* b0;
+    const float* b1;
+    const int32_t* state;
+    const float* xin;
+    const float* h_in;
+    const float* c_in;
+    const float* fe;
+    float* gp;
+    float* h_out;
+    float* c_out;
+    float* part;
+    float* dur;
+    int32_t mode, B, P, V, n_dur, reserved0;
+} spt_pk_dec_debug;
+spt_status spt_debug_pk_dec_stage(int32_t device, const spt_pk_dec_debug* args, char* err, size_t errlen);
+
+/* spt_debug_pk_tdt_steps: pk_state_init, then n_steps of the engine's whole decode step -- LSTM layer 0, LSTM
+ * layer 1, the prediction projection, the joint and pk_joint_fin, the five launches of ParakeetEngine's step in
+ * its order, with its ping-pong of the LSTM state buffers -- on plain weights (placed as spt_debug_pk_dec_stage
+ * places them): lstm [2][4] = W_ih, W_hh [4P][P], b_ih, b_hh [4P] per layer; pred_w [P][P], pred_b [P]; joint_w
+ * [N][P], joint_b [N], N = V + 1 + n_dur; emb [V + 1][P]; fe [B * T3p][P]; lens [B][4].  Returns state
+ * [n_steps + 1][B][7] (slot 0: after the init) and the four output arrays [B * cap + 1] after the last step. */
+typedef struct spt_pk_steps_debug {
+    const float* lstm[2][4];
+    const float* pred_w;
+    const float* pred_b;
+    const float* joint_w;
+    const float* joint_b;
+    const float* emb;
+    const float* fe;
+    const int32_t* lens;
+    int32_t* state;
+    int32_t* out_tok;
+    int32_t* out_frame;
+    float* out_t1;
+    float* out_t2;
+    int32_t B, P, V, n_dur, n_steps, max_symbols, cap, T3p;
+} spt_pk_steps_debug;
+spt_status spt_debug_pk_tdt_steps(int32_t device, const spt_pk_steps_debug* args, char* err, size_t errlen);
+
 /* ================================================================================================
  * ABI 6: Parakeet-V3 (NeMo FastConformer-TDT), the app's other local engine;
  * ABI 8: spt_parakeet_create takes the app's model directory (the int8 ONNX export) natively.

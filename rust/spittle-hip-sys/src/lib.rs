@@ -152,6 +152,152 @@ pub struct spt_dec_step_debug {
     pub reserved0: i32,
 }
 
+/// `spt_debug_pk_conv` modes and `spt_debug_pk_rel_attn` variants (SPT_HAS_PK_KERNELS)
+pub const SPT_PK_CONV0: i32 = 0;
+pub const SPT_PK_DWCONV1: i32 = 1;
+pub const SPT_PK_DWCONV2: i32 = 2;
+pub const SPT_PK_CONV_MODULE: i32 = 3;
+pub const SPT_PK_ATTN_AUTO: i32 = 0;
+pub const SPT_PK_ATTN_VALU: i32 = 1;
+pub const SPT_PK_ATTN_MFMA: i32 = 2;
+
+/// the arguments of `spt_debug_pk_conv` (one Parakeet subsampling or convolution-module launch)
+#[repr(C)]
+#[allow(non_snake_case)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_pk_conv_debug {
+    pub x: *const f32,
+    pub lens: *const i32,
+    pub w: *const f32,
+    pub bias: *const f32,
+    pub bn_g: *const f32,
+    pub bn_b: *const f32,
+    pub bn_m: *const f32,
+    pub bn_v: *const f32,
+    pub y: *mut f32,
+    pub y_count: i64,
+    pub dtype: i32,
+    pub mode: i32,
+    pub B: i32,
+    pub Tp: i32,
+    pub F: i32,
+    pub C: i32,
+}
+
+/// the arguments of `spt_debug_pk_rel_attn` (one Parakeet rel-pos attention launch)
+#[repr(C)]
+#[allow(non_snake_case)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_pk_attn_debug {
+    pub qkv: *const f32,
+    pub p: *const f32,
+    pub pu: *const f32,
+    pub pv: *const f32,
+    pub lens: *const i32,
+    pub out: *mut f32,
+    pub p_count: i64,
+    pub p_off: i64,
+    pub p_bstride: i64,
+    pub out_count: i64,
+    pub dtype: i32,
+    pub variant: i32,
+    pub B: i32,
+    pub Tp: i32,
+    pub H: i32,
+    pub dk: i32,
+    pub ldp: i32,
+    pub reserved0: i32,
+}
+
+/// `mode` of `spt_debug_pk_dec_stage`
+pub const SPT_PK_DEC_LSTM: i32 = 0;
+pub const SPT_PK_DEC_PRED: i32 = 1;
+pub const SPT_PK_DEC_JOINT: i32 = 2;
+
+/// the arguments of `spt_debug_pk_dec_stage` (one pk_decode_stage launch on plain weights)
+#[repr(C)]
+#[allow(non_snake_case)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_pk_dec_debug {
+    pub W: *const f32,
+    pub W2: *const f32,
+    pub b0: *const f32,
+    pub b1: *const f32,
+    pub state: *const i32,
+    pub xin: *const f32,
+    pub h_in: *const f32,
+    pub c_in: *const f32,
+    pub fe: *const f32,
+    pub gp: *mut f32,
+    pub h_out: *mut f32,
+    pub c_out: *mut f32,
+    pub part: *mut f32,
+    pub dur: *mut f32,
+    pub mode: i32,
+    pub B: i32,
+    pub P: i32,
+    pub V: i32,
+    pub n_dur: i32,
+    pub reserved0: i32,
+}
+
+/// the arguments of `spt_debug_pk_tdt_steps` (pk_state_init, then whole decode steps on plain weights)
+#[repr(C)]
+#[allow(non_snake_case)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_pk_steps_debug {
+    pub lstm: [[*const f32; 4]; 2],
+    pub pred_w: *const f32,
+    pub pred_b: *const f32,
+    pub joint_w: *const f32,
+    pub joint_b: *const f32,
+    pub emb: *const f32,
+    pub fe: *const f32,
+    pub lens: *const i32,
+    pub state: *mut i32,
+    pub out_tok: *mut i32,
+    pub out_frame: *mut i32,
+    pub out_t1: *mut f32,
+    pub out_t2: *mut f32,
+    pub B: i32,
+    pub P: i32,
+    pub V: i32,
+    pub n_dur: i32,
+    pub n_steps: i32,
+    pub max_symbols: i32,
+    pub cap: i32,
+    pub T3p: i32,
+}
+
+/// the arguments of `spt_debug_pk_tdt` (pk_state_init, then pk_joint_fin per step on given partials)
+#[repr(C)]
+#[allow(non_snake_case)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_pk_tdt_debug {
+    pub part: *const f32,
+    pub dur: *const f32,
+    pub lens: *const i32,
+    pub emb: *const f32,
+    pub fe: *const f32,
+    pub state: *mut i32,
+    pub xemb: *mut f32,
+    pub fecur: *mut f32,
+    pub out_tok: *mut i32,
+    pub out_frame: *mut i32,
+    pub out_t1: *mut f32,
+    pub out_t2: *mut f32,
+    pub B: i32,
+    pub P: i32,
+    pub V: i32,
+    pub n_dur: i32,
+    pub n_tiles: i32,
+    pub n_steps: i32,
+    pub max_symbols: i32,
+    pub cap: i32,
+    pub T3p: i32,
+    pub reserved0: i32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
 pub struct spt_model_params {
@@ -733,6 +879,24 @@ extern "C" {
         err: *mut c_char,
         errlen: usize,
     ) -> spt_status;
+
+    // the Parakeet encoder kernels and the TDT bookkeeping alone (SPT_HAS_PK_KERNELS)
+    pub fn spt_debug_pk_conv(device: i32, args: *const spt_pk_conv_debug, err: *mut c_char, errlen: usize) -> spt_status;
+    pub fn spt_debug_pk_relpos(
+        device: i32,
+        dtype: i32,
+        Tp: i32,
+        d: i32,
+        pe: *mut f32,
+        pe_count: i64,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_pk_rel_attn(device: i32, args: *const spt_pk_attn_debug, err: *mut c_char, errlen: usize) -> spt_status;
+
+    pub fn spt_debug_pk_tdt(device: i32, args: *const spt_pk_tdt_debug, err: *mut c_char, errlen: usize) -> spt_status;
+    pub fn spt_debug_pk_tdt_steps(device: i32, args: *const spt_pk_steps_debug, err: *mut c_char, errlen: usize) -> spt_status;
+    pub fn spt_debug_pk_dec_stage(device: i32, args: *const spt_pk_dec_debug, err: *mut c_char, errlen: usize) -> spt_status;
 
     // ---- ABI 6: Parakeet-V3
     pub fn spt_parakeet_default_model_params(p: *mut spt_pk_model_params);

@@ -67,6 +67,9 @@ EXPORTS = [
     "spt_debug_qgemv", "spt_get_weight_residency",
     # the decoder GEMV and the step's small kernels alone (SPT_HAS_GEMV_KERNELS)
     "spt_debug_gemv", "spt_debug_dec_step",
+    # the Parakeet encoder kernels and the TDT bookkeeping alone (SPT_HAS_PK_KERNELS)
+    "spt_debug_pk_conv", "spt_debug_pk_relpos", "spt_debug_pk_rel_attn", "spt_debug_pk_tdt",
+    "spt_debug_pk_dec_stage", "spt_debug_pk_tdt_steps",
     # the token-alignment kernels alone (SPT_HAS_ALIGN_KERNELS)
     "spt_debug_align_qk", "spt_debug_align_norm", "spt_debug_align_dtw", "spt_debug_align_words",
     # DTW token and word timestamps (SPT_HAS_TOKEN_TIMESTAMPS)
@@ -127,6 +130,48 @@ class DecStepDebug(C.Structure):
                 ("out_tok", _I32P), ("out_top1", _FP), ("out_top2", _FP), ("emb_blocks_bytes", C.c_size_t)] + \
                [(n, C.c_int32) for n in ("dtype", "op", "B", "Tq", "d", "ctx", "n_vocab", "n_tiles", "n_steps",
                                          "forced_len", "ignore_eot", "out_cap", "eot", "emb_q", "n_advance",
+                                         "reserved0")]
+
+
+SPT_PK_CONV0, SPT_PK_DWCONV1, SPT_PK_DWCONV2, SPT_PK_CONV_MODULE = range(4)
+SPT_PK_ATTN_AUTO, SPT_PK_ATTN_VALU, SPT_PK_ATTN_MFMA = range(3)
+
+
+class PkConvDebug(C.Structure):
+    """spt_pk_conv_debug"""
+    _fields_ = [("x", _FP), ("lens", _I32P)] + [(n, _FP) for n in ("w", "bias", "bn_g", "bn_b", "bn_m", "bn_v", "y")] + \
+               [("y_count", C.c_int64)] + [(n, C.c_int32) for n in ("dtype", "mode", "B", "Tp", "F", "C")]
+
+
+class PkAttnDebug(C.Structure):
+    """spt_pk_attn_debug"""
+    _fields_ = [(n, _FP) for n in ("qkv", "p", "pu", "pv")] + [("lens", _I32P), ("out", _FP)] + \
+               [(n, C.c_int64) for n in ("p_count", "p_off", "p_bstride", "out_count")] + \
+               [(n, C.c_int32) for n in ("dtype", "variant", "B", "Tp", "H", "dk", "ldp", "reserved0")]
+
+
+SPT_PK_DEC_LSTM, SPT_PK_DEC_PRED, SPT_PK_DEC_JOINT = range(3)
+
+
+class PkDecDebug(C.Structure):
+    """spt_pk_dec_debug"""
+    _fields_ = [(n, _FP) for n in ("W", "W2", "b0", "b1")] + [("state", _I32P)] + \
+               [(n, _FP) for n in ("xin", "h_in", "c_in", "fe", "gp", "h_out", "c_out", "part", "dur")] + \
+               [(n, C.c_int32) for n in ("mode", "B", "P", "V", "n_dur", "reserved0")]
+
+
+class PkStepsDebug(C.Structure):
+    """spt_pk_steps_debug"""
+    _fields_ = [("lstm", (_FP * 4) * 2)] + [(n, _FP) for n in ("pred_w", "pred_b", "joint_w", "joint_b", "emb", "fe")] + \
+               [("lens", _I32P), ("state", _I32P), ("out_tok", _I32P), ("out_frame", _I32P), ("out_t1", _FP), ("out_t2", _FP)] + \
+               [(n, C.c_int32) for n in ("B", "P", "V", "n_dur", "n_steps", "max_symbols", "cap", "T3p")]
+
+
+class PkTdtDebug(C.Structure):
+    """spt_pk_tdt_debug"""
+    _fields_ = [("part", _FP), ("dur", _FP), ("lens", _I32P), ("emb", _FP), ("fe", _FP), ("state", _I32P), ("xemb", _FP),
+                ("fecur", _FP), ("out_tok", _I32P), ("out_frame", _I32P), ("out_t1", _FP), ("out_t2", _FP)] + \
+               [(n, C.c_int32) for n in ("B", "P", "V", "n_dur", "n_tiles", "n_steps", "max_symbols", "cap", "T3p",
                                          "reserved0")]
 
 
@@ -497,6 +542,17 @@ def load():
     L.spt_debug_gemv.argtypes = [i32, C.POINTER(GemvDebug), C.c_char_p, C.c_size_t]
     L.spt_debug_dec_step.argtypes = [i32, C.POINTER(DecStepDebug), C.c_char_p, C.c_size_t]
     L.spt_debug_gemv.restype = L.spt_debug_dec_step.restype = C.c_int
+    # the Parakeet encoder kernels alone
+    L.spt_debug_pk_conv.argtypes = [i32, C.POINTER(PkConvDebug), C.c_char_p, C.c_size_t]
+    L.spt_debug_pk_relpos.argtypes = [i32, i32, i32, i32, fp, i64, C.c_char_p, C.c_size_t]
+    L.spt_debug_pk_rel_attn.argtypes = [i32, C.POINTER(PkAttnDebug), C.c_char_p, C.c_size_t]
+    L.spt_debug_pk_tdt.argtypes = [i32, C.POINTER(PkTdtDebug), C.c_char_p, C.c_size_t]
+    L.spt_debug_pk_conv.restype = L.spt_debug_pk_relpos.restype = L.spt_debug_pk_rel_attn.restype = C.c_int
+    L.spt_debug_pk_tdt.restype = C.c_int
+    L.spt_debug_pk_dec_stage.argtypes = [i32, C.POINTER(PkDecDebug), C.c_char_p, C.c_size_t]
+    L.spt_debug_pk_dec_stage.restype = C.c_int
+    L.spt_debug_pk_tdt_steps.argtypes = [i32, C.POINTER(PkStepsDebug), C.c_char_p, C.c_size_t]
+    L.spt_debug_pk_tdt_steps.restype = C.c_int
     L.spt_get_weight_residency.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.spt_get_weight_residency.restype = C.c_int
     # the token-alignment kernels alone

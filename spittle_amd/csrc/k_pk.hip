@@ -845,9 +845,13 @@ void pk_mel_norm(float* mel, const int* lens, int B, int Tp, int n_mels, hipStre
     SPT_LAUNCH_CHECK();
 }
 
+void pk_sub_check(int C, const char* who) {
+    if (C < 1 || C > 1024) throw std::runtime_error(std::string(who) + ": 1..1024 channels (a thread per channel)");
+}
+
 void pk_conv0(int dtype, const float* mel, const int* lens, int B, int Tp, int F, const float* w, const float* bias,
               int C, void* y, int T1p, int F1, hipStream_t st) {
-    if (C > 1024) throw std::runtime_error("pk_conv0: more than 1024 channels");
+    pk_sub_check(C, "pk_conv0");
     dim3 grid(T1p, B);
     const size_t sm = (size_t)3 * F * 4;
     if (dtype == DT_F16)
@@ -861,7 +865,7 @@ void pk_conv0(int dtype, const float* mel, const int* lens, int B, int Tp, int F
 
 void pk_dwconv(int dtype, const void* x, const int* lens, int stage, int B, int Tip, int Fi, const float* w,
                const float* bias, int C, void* y, int Top, int Fo, hipStream_t st) {
-    if (C > 1024) throw std::runtime_error("pk_dwconv: more than 1024 channels");
+    pk_sub_check(C, "pk_dwconv");
     dim3 grid(Top, B);
     if (dtype == DT_F16)
         hipLaunchKernelGGL(dwconv_kernel<f16>, grid, dim3(C), 0, st, (const f16*)x, lens, stage, Tip, Fi, w, bias, C,
@@ -883,14 +887,26 @@ void pk_relpos(int dtype, int Tp, int d, void* pe, hipStream_t st) {
     SPT_LAUNCH_CHECK();
 }
 
-void pk_rel_attn(int dtype, const void* qkv, const void* p, int ldp, const float* pu, const float* pv, const int* lens,
-                 int B, int Tp, int H, int dk, void* out, hipStream_t st, int64_t p_bstride) {
-    if (dk % 8 || dk > 256) throw std::runtime_error("pk_rel_attn: head dim must be a multiple of 8, <= 256");
+void pk_rel_attn_check(int dtype, const void* qkv, const void* p, int ldp, int Tp, int dk, int64_t p_bstride,
+                       int variant) {
+    if (dk < 8 || dk % 8 || dk > 256) throw std::runtime_error("pk_rel_attn: head dim must be a multiple of 8, <= 256");
     if (p_bstride && dtype != DT_F32) throw std::runtime_error("pk_rel_attn: per-utterance positions are f32 only");
+    if ((size_t)(2 * dk + Tp) * 4 > 64 * 1024) throw std::runtime_error("pk_rel_attn: too many frames for the LDS score row");
+    if (variant < PK_ATTN_AUTO || variant > PK_ATTN_MFMA) throw std::runtime_error("pk_rel_attn: variant 0..2");
+    if (variant == PK_ATTN_MFMA && (dtype != DT_F16 || (dk != 64 && dk != 128)))
+        throw std::runtime_error("pk_rel_attn: the MFMA kernel is f16 at head dim 64 or 128");
+    // k, p and (MFMA) q, v rows are read as 16-byte vectors
+    const int e16 = 16 / dtype_size(dtype);
+    if (ldp % e16 || p_bstride % e16 || (uintptr_t)qkv % 16 || (uintptr_t)p % 16)
+        throw std::runtime_error("pk_rel_attn: ldp, p_bstride and the base addresses must lie on the 16-byte grid");
+}
+
+void pk_rel_attn_variant(int dtype, const void* qkv, const void* p, int ldp, const float* pu, const float* pv,
+                         const int* lens, int B, int Tp, int H, int dk, void* out, hipStream_t st, int64_t p_bstride,
+                         int variant) {
+    pk_rel_attn_check(dtype, qkv, p, ldp, Tp, dk, p_bstride, variant);
     const size_t smem = (size_t)(2 * dk + Tp) * 4;
-    if (smem > 64 * 1024) throw std::runtime_error("pk_rel_attn: too many frames for the LDS score row");
-    static const bool valu = getenv("SPT_PK_ATTN_VALU") != nullptr;  // A/B switch
-    if (dtype == DT_F16 && !valu && (dk == 64 || dk == 128)) {
+    if (dtype == DT_F16 && variant != PK_ATTN_VALU && (dk == 64 || dk == 128)) {
         dim3 g(cdiv(Tp, 32), H, B);
         if (dk == 128)
             hipLaunchKernelGGL(rel_attn_mfma_kernel<128>, g, dim3(64), 0, st, (const f16*)qkv, (const f16*)p, ldp, pu, pv,
@@ -914,11 +930,22 @@ void pk_rel_attn(int dtype, const void* qkv, const void* p, int ldp, const float
     SPT_LAUNCH_CHECK();
 }
 
+void pk_rel_attn(int dtype, const void* qkv, const void* p, int ldp, const float* pu, const float* pv, const int* lens,
+                 int B, int Tp, int H, int dk, void* out, hipStream_t st, int64_t p_bstride) {
+    static const bool valu = getenv("SPT_PK_ATTN_VALU") != nullptr;  // A/B switch
+    pk_rel_attn_variant(dtype, qkv, p, ldp, pu, pv, lens, B, Tp, H, dk, out, st, p_bstride,
+                        valu ? PK_ATTN_VALU : PK_ATTN_AUTO);
+}
+
+void pk_conv_module_check(int d, int K) {
+    if (K != 9) throw std::runtime_error("pk_conv_module: depthwise kernel size 9 only");
+    if (d < CM_V || d % CM_V) throw std::runtime_error("pk_conv_module: channels must be a multiple of 4");
+}
+
 void pk_conv_module(int dtype, const void* a, const int* lens, int B, int Tp, int d, int K, const float* dw_w,
                     const float* dw_b, const float* bn_g, const float* bn_b, const float* bn_m, const float* bn_v,
                     void* out, hipStream_t st) {
-    if (K != 9) throw std::runtime_error("pk_conv_module: depthwise kernel size 9 only");
-    if (d % CM_V) throw std::runtime_error("pk_conv_module: channels must be a multiple of 4");
+    pk_conv_module_check(d, K);
     dim3 grid(cdiv(Tp, CM_TT), B, cdiv(d, 256 * CM_V));
     if (dtype == DT_F16)
         hipLaunchKernelGGL((conv_module_kernel<f16, 9>), grid, dim3(256), 0, st, (const f16*)a, lens, Tp, d, dw_w, dw_b,
@@ -968,15 +995,23 @@ void pk_prepare() {  // > 64 KiB dynamic LDS: per kernel and device, before any 
 
 int pk_joint_tile() { return kJointDO; }
 
-void pk_decode_stage(int mode, const PkDecArgs& a, hipStream_t s) {
+void pk_decode_stage_check(int mode, const PkDecArgs& a) {
+    if (mode != PKD_LSTM && mode != PKD_PRED && mode != PKD_JOINT) throw std::runtime_error("pk_decode_stage: bad mode");
     const int DO = mode == PKD_LSTM ? kLstmDO : mode == PKD_PRED ? kPredDO : kJointDO;
     const int nwm = mode == PKD_LSTM ? kNWL : mode == PKD_PRED ? kNWP : kNWJ;
     const int sem = mode == PKD_LSTM ? kSEL : mode == PKD_PRED ? kSEP : kSEJ;
-    if (a.K % (DG * 4) || a.ld % DO || a.B < 1 || a.B > 64 || (mode == PKD_LSTM && a.P % (DO / 4)) ||
-        a.K / 4 * DR > 512 * sem || (a.K / DG) % (256 / DO) || a.K / DG / (256 / DO) > nwm)
+    if (a.K < DG * 4 || a.K % (DG * 4) || a.ld < DO || a.ld % DO || a.B < 1 || a.B > 64 ||
+        (mode == PKD_LSTM && a.P % (DO / 4)) || a.K / 4 * DR > 512 * sem || (a.K / DG) % (256 / DO) ||
+        a.K / DG / (256 / DO) > nwm || a.N < 1 || a.N > a.ld)
         throw std::runtime_error("pk_decode_stage: bad shape");
+    if (((size_t)a.K * XP + (size_t)DG * DR * DO) * 4 > (size_t)kDecSmemMax)
+        throw std::runtime_error("pk_decode_stage: K too large for the LDS row stage");
+}
+
+void pk_decode_stage(int mode, const PkDecArgs& a, hipStream_t s) {
+    pk_decode_stage_check(mode, a);
+    const int DO = mode == PKD_LSTM ? kLstmDO : mode == PKD_PRED ? kPredDO : kJointDO;
     const size_t smem = ((size_t)a.K * XP + (size_t)DG * DR * DO) * 4;
-    if (smem > (size_t)kDecSmemMax) throw std::runtime_error("pk_decode_stage: K too large for the LDS row stage");
     // row groups (DR utterances each) spread over grid.y, kDecRowsWg utterances per workgroup: one
     // workgroup row running all 8 groups of a batch of 64 in turn took 50 us per LSTM stage (10 at
     // B = 8), 16 per workgroup 39, 8 per workgroup the same (every workgroup re-reads its weight
@@ -993,7 +1028,13 @@ void pk_decode_stage(int mode, const PkDecArgs& a, hipStream_t s) {
     SPT_LAUNCH_CHECK();
 }
 
+void pk_joint_fin_check(const PkFinArgs& a) {
+    if (a.B < 1 || a.n_tiles < 1 || a.n_dur < 1 || a.P < 1 || a.cap < 0 || a.V < 0)
+        throw std::runtime_error("pk_joint_fin: need B, n_tiles, n_dur, P >= 1 and cap, V >= 0");
+}
+
 void pk_joint_fin(const PkFinArgs& a, hipStream_t s) {
+    pk_joint_fin_check(a);
     hipLaunchKernelGGL(joint_fin_kernel, dim3(a.B), dim3(256), 0, s, a);
     SPT_LAUNCH_CHECK();
 }

@@ -34,6 +34,19 @@ void pk_relpos(int dtype, int Tp, int d, void* pe, hipStream_t st);
 // p_bstride != 0 (f32 only): utterance b reads its own projected positions at p + b * p_bstride
 void pk_rel_attn(int dtype, const void* qkv, const void* p, int ldp, const float* pu, const float* pv,
                  const int* lens, int B, int Tp, int H, int dk, void* out, hipStream_t st, int64_t p_bstride = 0);
+// the same launch with the kernel named: AUTO is the MFMA kernel for f16 at head dim 64 / 128 and the
+// VALU kernel otherwise; pk_rel_attn passes AUTO, or VALU under SPT_PK_ATTN_VALU (read once per process)
+enum { PK_ATTN_AUTO = 0, PK_ATTN_VALU = 1, PK_ATTN_MFMA = 2 };
+void pk_rel_attn_variant(int dtype, const void* qkv, const void* p, int ldp, const float* pu, const float* pv,
+                         const int* lens, int B, int Tp, int H, int dk, void* out, hipStream_t st, int64_t p_bstride,
+                         int variant);
+// what the launchers refuse (std::runtime_error), host-only, shared with the spt_debug_pk_* hooks.
+// pk_rel_attn_check: head dim, the LDS score row, f32-only per-utterance positions, the kernel a
+// variant names, and the 16-byte grid of the vector loads (ldp, p_bstride and the two base addresses)
+void pk_rel_attn_check(int dtype, const void* qkv, const void* p, int ldp, int Tp, int dk, int64_t p_bstride,
+                       int variant);
+void pk_sub_check(int C, const char* who);      // pk_conv0 / pk_dwconv: a thread per channel, <= 1024
+void pk_conv_module_check(int d, int K);
 // conformer convolution module after pw1: a [B*Tp][2d] -> GLU -> depthwise K taps (frames
 // outside [0, T3_b) zero) -> BatchNorm (eval) -> Swish -> out [B*Tp][d]
 void pk_conv_module(int dtype, const void* a, const int* lens, int B, int Tp, int d, int K, const float* dw_w,
@@ -102,6 +115,9 @@ struct PkDecArgs {
     float* dur;                     // JOINT: duration logits [B][n_dur]
 };
 void pk_decode_stage(int mode, const PkDecArgs& a, hipStream_t s);
+// what pk_decode_stage refuses (host-only, shared with spt_debug_pk_dec_stage): the mode, K, ld, B, P
+// against the stage's register and LDS budgets, and N outside 1 .. ld
+void pk_decode_stage_check(int mode, const PkDecArgs& a);
 // one-time kernel attributes (before any stream capture)
 void pk_prepare();
 // outputs per workgroup of the joint stage (its top-2 partials per row: ld / pk_joint_tile())
@@ -118,6 +134,9 @@ struct PkFinArgs {
     int* out_tok; int* out_frame; float* out_t1; float* out_t2;  // [B][cap]
 };
 void pk_joint_fin(const PkFinArgs& a, hipStream_t s);
+// what pk_joint_fin refuses (host-only, shared with spt_debug_pk_tdt): B, n_tiles, n_dur, P below 1 (with
+// no duration logit a token below max_symbols would never advance its row), cap below 0
+void pk_joint_fin_check(const PkFinArgs& a);
 // rows start at t = 0 with the blank symbol pending (upd, tok = V); h / c: n floats zeroed; xemb
 // zero (the blank row), fecur = frame 0 of fe [B*T3p][P]
 void pk_state_init(PkState* st, int B, int V, float* h, float* c, int n, float* xemb, float* fecur, const float* fe,

@@ -62,7 +62,10 @@ def test_struct_layouts_match_header(tmp_path):
                "spt_pk_model_params": L.PkModelParams, "spt_pk_infer_params": L.PkInferParams,
                "spt_pk_segment": L.PkSegment, "spt_pk_result": L.PkResult, "spt_pk_model_info": L.PkModelInfo,
                "spt_pk_timings": L.PkTimings, "spt_sample_params": L.SampleParams,
-               "spt_gemv_debug": L.GemvDebug, "spt_dec_step_debug": L.DecStepDebug}
+               "spt_gemv_debug": L.GemvDebug, "spt_dec_step_debug": L.DecStepDebug,
+               "spt_pk_conv_debug": L.PkConvDebug, "spt_pk_attn_debug": L.PkAttnDebug,
+               "spt_pk_tdt_debug": L.PkTdtDebug, "spt_pk_dec_debug": L.PkDecDebug,
+               "spt_pk_steps_debug": L.PkStepsDebug}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void) {"]
     for cname, py in structs.items():
         lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
