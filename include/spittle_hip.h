@@ -56,6 +56,9 @@ typedef enum {
 #define SPT_NO_TIMESTAMPS   2u  /* whisper_full_params.no_timestamps */
 #define SPT_IGNORE_EOT      4u  /* benchmark protocol: keep decoding past <|endoftext|> */
 #define SPT_SUPPRESS_NST    8u  /* whisper_full_params.suppress_non_speech_tokens (ggml models) */
+#define SPT_NO_SPEECH_PROB 16u  /* SPT_HAS_NO_SPEECH: compute and report each window's no-speech probability
+                                   (spt_get_window_info) without skipping; an enabled no_speech_thold
+                                   implies it.  The fast path stays the fast path */
 
 typedef struct {
     int32_t dtype;        /* SPT_DTYPE_BF16 (default), SPT_DTYPE_F16 or SPT_DTYPE_F32: weights + activations at
@@ -96,7 +99,7 @@ typedef struct {
     int32_t translate;           /* task <|translate|> instead of <|transcribe|> */
     const char* initial_prompt;  /* jargon prompt text (src-tauri/src/jargon.rs:594); ggml models */
     uint32_t flags;              /* SPT_SUPPRESS_BLANK | SPT_NO_TIMESTAMPS | SPT_SUPPRESS_NST |
-                                    SPT_IGNORE_EOT; default SPT_SUPPRESS_BLANK (whisper_full's
+                                    SPT_IGNORE_EOT | SPT_NO_SPEECH_PROB; default SPT_SUPPRESS_BLANK (whisper_full's
                                     defaults: timestamps on) */
     int32_t max_new_tokens;      /* fast path: generated tokens per 30 s window (<= 220);
                                     whisper_full path: whisper_full_params.max_tokens (0 = none) */
@@ -116,11 +119,17 @@ typedef struct {
     float entropy_thold;         /* a decoder whose last 32 tokens' entropy is lower fails (2.4) */
     float logprob_thold;         /* fall back when the average log-probability is lower (-1.0) */
     float max_initial_ts;        /* the first timestamp is at most this many seconds (1.0) */
-    /* whisper_full_params.no_speech_thold has no counterpart: whisper.cpp 1.7.1 (vendored by
+    /* whisper_full_params.no_speech_thold (SPT_HAS_NO_SPEECH; the former int32 reserved0: same offset
+     * and size, and 0 -- every existing caller -- is off).  whisper.cpp 1.7.1 (vendored by
      * whisper-rs-sys 0.11.1, the reference's engine) declares it "TODO: not implemented" and never
-     * reads it, so the reference skips no window for no-speech probability [recalled; whisper.cpp
-     * is not in /root/reference].  A later whisper.cpp's skip would be added here, not emulated. */
-    int32_t reserved0;
+     * reads it, so the reference skips no window for no-speech probability; every later whisper.cpp
+     * implements it [both recalled; whisper.cpp is not in /root/reference].  Hence off by default:
+     * enabled iff 0 < no_speech_thold < 1 (>= 1 is off too: a probability never exceeds it); a
+     * negative value or NaN is SPT_ERR_INVALID_ARG.  Enabled, a window of the whisper_full path is
+     * dropped when its no-speech probability > no_speech_thold and the kept decoder's average
+     * log-probability < logprob_thold; the call takes the whisper_full path.  Unlike whisper.cpp
+     * (default 0.6, where 0 means "skip whenever the log-probability is low"), 0 is off here. */
+    float no_speech_thold;
     uint64_t seed;               /* temperature sampling stream */
 } spt_infer_params;
 
@@ -236,6 +245,34 @@ spt_status spt_get_call_stats(const spt_ctx* ctx, spt_call_stats* s);
  * bounded wait ran out (0 in normal operation).  Either pointer may be NULL. */
 spt_status spt_get_xq_stats(const spt_ctx* ctx, int32_t* fused_launches, int32_t* fallbacks);
 
+/* The no-speech probability and the silence skip (additive over ABI 14, announced by
+ * SPT_HAS_NO_SPEECH and the word "nospeech" in spt_version()).  The probability of
+ * a window is softmax(raw logits)[<|nospeech|>] of the last prompt token of the decode run that
+ * produced the kept decoder (after any [prev] prefix and the language-detect pass): no suppression
+ * mask, no blank rule, no temperature; f32 in every engine dtype, in a summation order fixed by
+ * n_vocab, so a row's bits in a batch are its bits alone.  It is computed when SPT_NO_SPEECH_PROB is
+ * set or no_speech_thold is enabled; the skip itself is whisper_full-only (an enabled threshold routes
+ * the call there; spt_transcribe_batch_device refuses it).
+ * spt_get_window_info returns one record per window of the last spt_transcribe* call, in decode order
+ * per utterance (utterances ascending); the records are host bookkeeping and always kept (a call that
+ * fails leaves none).  *n is the
+ * count even when it exceeds cap; the first min(cap, *n) records are written (out may be NULL when
+ * cap is 0). */
+#define SPT_HAS_NO_SPEECH 1
+typedef struct spt_window_info {
+    int32_t utterance;          /* index in the call's batch */
+    int32_t seek, seek_delta;   /* 10 ms frames */
+    int32_t i0, n_tokens;       /* the window's tokens in that utterance's spt_result.tokens (0 tokens when skipped) */
+    int32_t n_fallbacks;        /* index of the temperature kept */
+    float temperature;
+    float avg_logprob;          /* kept decoder's; NaN for a window the fast path decoded (in a fast-path call an
+                                   utterance over 30 s or under 1 s takes whisper_full's seek loop: its windows carry
+                                   the loop's own avg_logprob and seek_delta) */
+    float no_speech_prob;       /* NaN when not computed */
+    int32_t skipped;
+} spt_window_info;
+spt_status spt_get_window_info(const spt_ctx* ctx, spt_window_info* out, int32_t cap, int32_t* n);
+
 /* Multi-GPU load: the weight arena is one device allocation whose layout is a
  * pure function of (model, dtype), spt_model_info.weight_bytes long.  Rank 0 loads the model
  * (file parse + device dequantisation) and exports the arena into a device buffer; the buffer
@@ -340,6 +377,10 @@ spt_status spt_debug_sample_beam(int32_t device, const float* logits, int32_t B,
                                  const spt_sample_params* prm, const int32_t* row, int32_t step, int32_t k,
                                  int32_t chunked, int32_t* cand_id, float* cand_lp, int32_t* tid, char* err,
                                  size_t errlen);
+/* the no-speech kernel alone (SPT_HAS_NO_SPEECH; the rules of the hooks above): logits [B][ldl] f32, only
+ * columns < n_vocab are read; prob [B].  B 1..1024, n_vocab 1..53248, ldl >= n_vocab, nosp in [0, n_vocab). */
+spt_status spt_debug_no_speech(int32_t device, const float* logits, int32_t B, int32_t n_vocab, int32_t ldl,
+                               int32_t nosp, float* prob, char* err, size_t errlen);
 /* one beam K/V gather: src and dst [L][2][B][H][ctx][64] f32, converted to dtype for the launch
  * and back; dst row b takes positions < pos0 of src row rows[b] and keeps the rest. */
 spt_status spt_debug_sample_kv_gather(int32_t device, int32_t dtype, const float* src, float* dst,

@@ -60,6 +60,8 @@ pub const SPT_SUPPRESS_BLANK: u32 = 1;
 pub const SPT_NO_TIMESTAMPS: u32 = 2;
 pub const SPT_IGNORE_EOT: u32 = 4;
 pub const SPT_SUPPRESS_NST: u32 = 8;
+/// report each window's no-speech probability without skipping (SPT_HAS_NO_SPEECH)
+pub const SPT_NO_SPEECH_PROB: u32 = 16;
 
 pub const SPT_MODEL_WEIGHTS_EXTERNAL: u32 = 1;
 /// quantised decoder matrices of a ggml file stay resident in their blocks (SPT_HAS_QUANT_RESIDENT)
@@ -327,8 +329,25 @@ pub struct spt_infer_params {
     pub entropy_thold: f32,
     pub logprob_thold: f32,
     pub max_initial_ts: f32,
-    pub reserved0: i32,
+    /// the silence skip's threshold (the formerly reserved int32 slot): on iff 0 < value < 1, 0 = off
+    pub no_speech_thold: f32,
     pub seed: u64,
+}
+
+/// one window of the last `spt_transcribe*` call (`spt_get_window_info`, SPT_HAS_NO_SPEECH)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct spt_window_info {
+    pub utterance: i32,
+    pub seek: i32,
+    pub seek_delta: i32,
+    pub i0: i32,
+    pub n_tokens: i32,
+    pub n_fallbacks: i32,
+    pub temperature: f32,
+    pub avg_logprob: f32,
+    pub no_speech_prob: f32,
+    pub skipped: i32,
 }
 
 #[repr(C)]
@@ -488,6 +507,19 @@ extern "C" {
     pub fn spt_get_call_stats(ctx: *const spt_ctx, s: *mut spt_call_stats) -> spt_status;
     // additive to ABI 14: fused cross-Q + cross-attention launches and chain reruns of the last call
     pub fn spt_get_xq_stats(ctx: *const spt_ctx, fused_launches: *mut i32, fallbacks: *mut i32) -> spt_status;
+    // the no-speech probability and the silence skip (SPT_HAS_NO_SPEECH, additive over ABI 14)
+    pub fn spt_get_window_info(ctx: *const spt_ctx, out: *mut spt_window_info, cap: i32, n: *mut i32) -> spt_status;
+    pub fn spt_debug_no_speech(
+        device: i32,
+        logits: *const f32,
+        B: i32,
+        n_vocab: i32,
+        ldl: i32,
+        nosp: i32,
+        prob: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
 
     pub fn spt_weights_export(ctx: *mut spt_ctx, dev_dst: *mut c_void, bytes: usize) -> spt_status;
     pub fn spt_weights_import(ctx: *mut spt_ctx, dev_src: *const c_void, bytes: usize) -> spt_status;
@@ -1153,6 +1185,8 @@ pub const SPT_HAS_SENSEVOICE: c_int = 1;
 pub const SPT_HAS_ALIGN_KERNELS: c_int = 1;
 /// DTW token and word timestamps (`spt_transcribe_aligned`) are present
 pub const SPT_HAS_TOKEN_TIMESTAMPS: c_int = 1;
+/// the no-speech probability, the silence skip and `spt_get_window_info` are present
+pub const SPT_HAS_NO_SPEECH: c_int = 1;
 
 /// a text token's start and end (10 ms units), probability and index into `spt_result.tokens`
 #[repr(C)]

@@ -195,6 +195,29 @@ unsafe fn take_alignment(a: *mut sys::spt_alignment) -> (Vec<TokenTime>, Vec<Wor
 /// One Whisper model on one MI355X.
 pub struct HipWhisperEngine {
     ctx: *mut sys::spt_ctx,
+    no_speech_thold: f32,
+    no_speech_prob: bool,
+}
+
+/// One window of the last call (`spt_get_window_info`, `SPT_HAS_NO_SPEECH`).
+#[derive(Debug, Clone, PartialEq)]
+pub struct WindowInfo {
+    /// index in the call's batch
+    pub utterance: usize,
+    /// 10 ms frames
+    pub seek: i32,
+    pub seek_delta: i32,
+    /// the window's tokens among the utterance's result tokens (none when skipped)
+    pub first_token: usize,
+    pub n_tokens: usize,
+    /// index of the temperature kept, and that temperature
+    pub n_fallbacks: i32,
+    pub temperature: f32,
+    /// the kept decoder's average log-probability (NaN on the fast path)
+    pub avg_logprob: f32,
+    /// NaN when not computed
+    pub no_speech_prob: f32,
+    pub skipped: bool,
 }
 
 // SAFETY: a context is not thread-affine (every entry point selects its device); the app
@@ -203,7 +226,7 @@ unsafe impl Send for HipWhisperEngine {}
 
 impl HipWhisperEngine {
     pub fn new() -> Self {
-        Self { ctx: std::ptr::null_mut() }
+        Self { ctx: std::ptr::null_mut(), no_speech_thold: 0.0, no_speech_prob: false }
     }
 
     fn last_error(&self) -> String {
@@ -216,6 +239,60 @@ impl HipWhisperEngine {
             return Err("Model is not loaded for transcription.".into());
         }
         Ok(())
+    }
+
+    /// whisper.cpp >= 1.7.3's `no_speech_thold` for the calls that follow: a window whose no-speech
+    /// probability is above `thold` and whose average log-probability is below `logprob_thold` is
+    /// dropped.  On iff 0 < thold < 1; 0 (the default: the reference's whisper.cpp 1.7.1 never reads
+    /// the parameter) is off.  `report`: compute each window's probability for `window_info` even
+    /// with the threshold off.  A negative or NaN threshold fails the next call.
+    pub fn set_no_speech(&mut self, thold: f32, report: bool) {
+        self.no_speech_thold = thold;
+        self.no_speech_prob = report;
+    }
+
+    fn apply_no_speech(&self, rq: &mut Request) {
+        rq.ip.no_speech_thold = self.no_speech_thold;
+        if self.no_speech_prob {
+            rq.ip.flags |= sys::SPT_NO_SPEECH_PROB;
+        }
+    }
+
+    /// One record per window of the last transcribe call, in decode order per utterance.
+    pub fn window_info(&self) -> Result<Vec<WindowInfo>, Box<dyn Error>> {
+        self.need()?;
+        let mut n = 0i32;
+        // SAFETY: a live context; cap 0 writes nothing
+        let st = unsafe { sys::spt_get_window_info(self.ctx, std::ptr::null_mut(), 0, &mut n) };
+        if st != sys::SPT_OK {
+            return Err(status_error("window info", st, self.last_error()));
+        }
+        let zero = sys::spt_window_info {
+            utterance: 0, seek: 0, seek_delta: 0, i0: 0, n_tokens: 0, n_fallbacks: 0, temperature: 0.0,
+            avg_logprob: 0.0, no_speech_prob: 0.0, skipped: 0,
+        };
+        let mut buf = vec![zero; n.max(0) as usize];
+        // SAFETY: buf holds `cap` writable records
+        let st = unsafe { sys::spt_get_window_info(self.ctx, buf.as_mut_ptr(), buf.len() as i32, &mut n) };
+        if st != sys::SPT_OK {
+            return Err(status_error("window info", st, self.last_error()));
+        }
+        buf.truncate(n.max(0) as usize);
+        Ok(buf
+            .iter()
+            .map(|w| WindowInfo {
+                utterance: w.utterance as usize,
+                seek: w.seek,
+                seek_delta: w.seek_delta,
+                first_token: w.i0 as usize,
+                n_tokens: w.n_tokens as usize,
+                n_fallbacks: w.n_fallbacks,
+                temperature: w.temperature,
+                avg_logprob: w.avg_logprob,
+                no_speech_prob: w.no_speech_prob,
+                skipped: w.skipped != 0,
+            })
+            .collect())
     }
 
     fn load_model_raw(&mut self, model_path: &Path, mp: sys::spt_model_params) -> Result<(), Box<dyn Error>> {
@@ -276,7 +353,8 @@ impl HipWhisperEngine {
         params: Option<WhisperInferenceParams>,
     ) -> Result<Vec<TranscriptionResult>, Box<dyn Error>> {
         self.need()?;
-        let rq = request(params)?;
+        let mut rq = request(params)?;
+        self.apply_no_speech(&mut rq);
         let ptrs: Vec<*const f32> = batch.iter().map(|a| a.as_ptr()).collect();
         let lens: Vec<usize> = batch.iter().map(|a| a.len()).collect();
         let mut out = vec![std::ptr::null_mut::<sys::spt_result>(); batch.len()];
@@ -322,7 +400,8 @@ impl HipWhisperEngine {
         params: Option<WhisperInferenceParams>,
     ) -> Result<Vec<AlignedTranscription>, Box<dyn Error>> {
         self.need()?;
-        let rq = request(params)?;
+        let mut rq = request(params)?;
+        self.apply_no_speech(&mut rq);
         let ptrs: Vec<*const f32> = batch.iter().map(|a| a.as_ptr()).collect();
         let lens: Vec<usize> = batch.iter().map(|a| a.len()).collect();
         let mut out = vec![std::ptr::null_mut::<sys::spt_result>(); batch.len()];
@@ -386,7 +465,8 @@ impl TranscriptionEngine for HipWhisperEngine {
         params: Option<WhisperInferenceParams>,
     ) -> Result<TranscriptionResult, Box<dyn Error>> {
         self.need()?;
-        let rq = request(params)?;
+        let mut rq = request(params)?;
+        self.apply_no_speech(&mut rq);
         let mut out = std::ptr::null_mut();
         // SAFETY: samples outlives the call; out receives a library-owned result
         let st = unsafe { sys::spt_transcribe(self.ctx, samples.as_ptr(), samples.len(), &rq.ip, &mut out) };

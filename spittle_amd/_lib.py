@@ -16,6 +16,7 @@ SPT_OK, SPT_ERR_INVALID_ARG, SPT_ERR_LOAD, SPT_ERR_DEVICE, SPT_ERR_OOM, SPT_ERR_
 STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "LOAD", 3: "DEVICE", 4: "OOM", 5: "UNSUPPORTED", 6: "INTERNAL"}
 SPT_DTYPE_F32, SPT_DTYPE_BF16, SPT_DTYPE_F16, SPT_DTYPE_I8 = 0, 1, 2, 3
 SPT_SUPPRESS_BLANK, SPT_NO_TIMESTAMPS, SPT_IGNORE_EOT, SPT_SUPPRESS_NST = 1, 2, 4, 8
+SPT_NO_SPEECH_PROB = 16  # SPT_HAS_NO_SPEECH: report each window's no-speech probability without skipping
 
 # every symbol include/spittle_hip.h declares
 EXPORTS = [
@@ -75,6 +76,8 @@ EXPORTS = [
     # DTW token and word timestamps (SPT_HAS_TOKEN_TIMESTAMPS)
     "spt_set_alignment_heads", "spt_transcribe_aligned", "spt_transcribe_aligned_batch", "spt_alignment_free",
     "spt_debug_align_last", "spt_debug_align_stats",
+    # the no-speech probability and the silence skip (SPT_HAS_NO_SPEECH)
+    "spt_get_window_info", "spt_debug_no_speech",
 ]
 
 
@@ -186,8 +189,13 @@ class InferParams(C.Structure):
                 ("beam_size", C.c_int32), ("forced_tokens", C.POINTER(C.c_int32)), ("n_forced", C.c_int32),
                 ("prompt_tokens", C.POINTER(C.c_int32)), ("n_prompt_tokens", C.c_int32),
                 ("temperature_inc", C.c_float), ("best_of", C.c_int32), ("entropy_thold", C.c_float),
-                ("logprob_thold", C.c_float), ("max_initial_ts", C.c_float), ("reserved0", C.c_int32),
+                ("logprob_thold", C.c_float), ("max_initial_ts", C.c_float), ("no_speech_thold", C.c_float),
                 ("seed", C.c_uint64)]
+
+
+class WindowInfo(C.Structure):  # spt_window_info
+    _fields_ = [(n, C.c_int32) for n in ("utterance", "seek", "seek_delta", "i0", "n_tokens", "n_fallbacks")] + \
+               [(n, C.c_float) for n in ("temperature", "avg_logprob", "no_speech_prob")] + [("skipped", C.c_int32)]
 
 
 class Segment(C.Structure):
@@ -363,6 +371,8 @@ def load():
     L.spt_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.spt_get_call_stats.argtypes = [vp, C.POINTER(CallStats)]
     L.spt_get_xq_stats.argtypes = [vp, ip, ip]
+    L.spt_get_window_info.argtypes = [vp, C.POINTER(WindowInfo), C.c_int32, ip]
+    L.spt_get_window_info.restype = C.c_int
     L.spt_debug_mel.argtypes = [vp, fp, C.c_size_t, fp]
     L.spt_debug_mel_at.argtypes = [vp, fp, C.c_size_t, C.c_int32, fp]
     L.spt_debug_encode.argtypes = [vp, fp, fp]
@@ -517,7 +527,8 @@ def load():
     L.spt_debug_sample_beam.argtypes = [i32, fp, i32, i32, i32, i32, i32, i32, u32p, spp, i32p, i32, i32, i32, i32p, fp,
                                         i32p, C.c_char_p, C.c_size_t]
     L.spt_debug_sample_kv_gather.argtypes = [i32, i32, fp, fp, i32p, i32, i32, i32, i32, i32, C.c_char_p, C.c_size_t]
-    for fn in ("spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather"):
+    L.spt_debug_no_speech.argtypes = [i32, fp, i32, i32, i32, i32, fp, C.c_char_p, C.c_size_t]
+    for fn in ("spt_debug_sample_tokens", "spt_debug_sample_beam", "spt_debug_sample_kv_gather", "spt_debug_no_speech"):
         getattr(L, fn).restype = C.c_int
     # the attention kernels alone
     L.spt_debug_attn_enc.argtypes = [i32, i32, fp, i32, i32, i32, fp, C.c_char_p, C.c_size_t]

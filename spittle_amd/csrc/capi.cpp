@@ -85,9 +85,35 @@ spt_status lang_of(spt_ctx* c, const spt_infer_params* p, int* lang_tok) {
     return SPT_OK;
 }
 
-// the device-resident greedy no-timestamp protocol, or whisper_full's window loop
+// the silence skip is on iff 0 < no_speech_thold < 1 (0: off, every caller before SPT_HAS_NO_SPEECH; >= 1:
+// a probability never exceeds it)
+bool skip_enabled(const spt_infer_params* p) { return p->no_speech_thold > 0.0f && p->no_speech_thold < 1.0f; }
+
+// the device-resident greedy no-timestamp protocol, or whisper_full's window loop (the fast path has logits
+// but no log-probabilities: an enabled threshold needs the loop)
 bool full_mode(const spt_infer_params* p) {
-    return !(p->flags & SPT_NO_TIMESTAMPS) || p->temperature_inc > 0.0f || p->temperature != 0.0f || p->beam_size > 1;
+    return !(p->flags & SPT_NO_TIMESTAMPS) || p->temperature_inc > 0.0f || p->temperature != 0.0f || p->beam_size > 1 ||
+           skip_enabled(p);
+}
+
+// start of every spt_transcribe* call: the parameters checked before any device work, the window records reset
+spt_status begin_call(spt_ctx* c, const spt_infer_params* p) {
+    c->windows.clear();
+    if (!(p->no_speech_thold >= 0.0f)) return spt_fail(c, SPT_ERR_INVALID_ARG, "no_speech_thold must be >= 0 (0: off)");
+    return SPT_OK;
+}
+
+// records in decode order per utterance, utterances ascending (a mixed batch runs its one-window
+// utterances before the seek-loop ones)
+// a call that fails reports no windows: the records are those of the last call that succeeded or none
+spt_status end_call(spt_ctx* c, spt_status s) {
+    if (c && s != SPT_OK) c->windows.clear();
+    return s;
+}
+
+void sort_windows(spt_ctx* c) {
+    std::stable_sort(c->windows.begin(), c->windows.end(),
+                     [](const spt_window_info& a, const spt_window_info& b) { return a.utterance < b.utterance; });
 }
 
 // whisper_full's prompt_init: [sot] (+ [lang, task] for multilingual) + [notimestamps]; its
@@ -135,7 +161,8 @@ spt_status build_request(spt_ctx* c, const spt_infer_params* p, spt::DecodeReque
     const int used = (int)(rq->prefix.size() + rq->prompt.size());
     if (used + n > dm.n_text_ctx + 1) n = dm.n_text_ctx + 1 - used;
     rq->n_steps = n;
-    rq->flags = p->flags;
+    rq->flags = p->flags & ~SPT_NO_SPEECH_PROB;  // not a decoding rule: the passes and their graphs are the same
+    rq->want_nosp = (p->flags & SPT_NO_SPEECH_PROB) != 0;
     rq->forced = p->forced_tokens;
     rq->n_forced = p->forced_tokens ? p->n_forced : 0;
     if (rq->n_forced < 0 || rq->n_forced > dm.n_text_ctx) return fail(c, SPT_ERR_INVALID_ARG, "n_forced out of range");
@@ -243,7 +270,8 @@ spt_alignment* make_alignment(const spt_ctx* c, const spt::FullResult& f) {
 
 // whisper_full (full.cpp) over host utterances; align (optional): DTW token timestamps too
 spt_status run_full(spt_ctx* c, const float* const* pcm, const size_t* n_samples, size_t batch,
-                    const spt_infer_params* p, spt_result** out, spt_alignment** align = nullptr) {
+                    const spt_infer_params* p, spt_result** out, spt_alignment** align = nullptr,
+                    const size_t* utt_index = nullptr) {  // utt_index: the utterances' indices in the call's batch
     if (p->beam_size > 8) return fail(c, SPT_ERR_INVALID_ARG, "beam_size must be at most 8");
     if (p->beam_size > c->eng->max_batch())
         return fail(c, SPT_ERR_INVALID_ARG, "beam_size exceeds the context's max_batch (one row per beam)");
@@ -288,6 +316,8 @@ spt_status run_full(spt_ctx* c, const float* const* pcm, const size_t* n_samples
         fp.n_forced = p->n_forced;
     }
     fp.ignore_eot = align && (p->flags & SPT_IGNORE_EOT) != 0;
+    fp.no_speech_prob = (p->flags & SPT_NO_SPEECH_PROB) != 0;
+    fp.no_speech_thold = skip_enabled(p) ? p->no_speech_thold : 0.0f;
     std::vector<const float*> ptr(batch);
     std::vector<int> ns(batch);
     for (size_t u = 0; u < batch; ++u) {
@@ -299,6 +329,11 @@ spt_status run_full(spt_ctx* c, const float* const* pcm, const size_t* n_samples
     std::vector<spt::FullResult> res;
     spt::whisper_full_batch(*c->eng, c->vocab.get(), ptr, ns, fp, std::vector<int>(ptoks.begin(), ptoks.end()),
                             lang_tok >= 0 ? lang_tok : -1, &res);
+    for (size_t u = 0; u < batch; ++u)
+        for (const spt::FullWindow& w : res[u].windows)
+            c->windows.push_back(spt_window_info{(int32_t)(utt_index ? utt_index[u] : u), w.seek, w.seek_delta, w.i0,
+                                                 w.n_tokens, w.n_fallbacks, w.temperature, w.avg_logprob,
+                                                 w.no_speech_prob, w.skipped ? 1 : 0});
     for (size_t u = 0; u < batch; ++u) {
         out[u] = make_full_result(res[u], sp);
         if (align) align[u] = out[u] ? make_alignment(c, res[u]) : nullptr;
@@ -365,17 +400,18 @@ spt_status run_windows(spt_ctx* c, std::vector<Window>& win, const float* const*
             }
         }
         std::vector<int> otok((size_t)B * rq.n_steps), lang(B, -1);
-        std::vector<float> o1((size_t)B * rq.n_steps), o2((size_t)B * rq.n_steps);
+        std::vector<float> o1((size_t)B * rq.n_steps), o2((size_t)B * rq.n_steps), nosp(B, NAN);
         if (uid != loaded) {
             e.load_utterances(up.data(), un.data(), (int)up.size());
             loaded = uid;
         }
         e.encode_windows(wu.data(), ws.data(), B);
-        e.decode(B, rq, otok.data(), o1.data(), o2.data(), lang.data());
+        e.decode(B, rq, otok.data(), o1.data(), o2.data(), lang.data(), nullptr, rq.want_nosp ? nosp.data() : nullptr);
         for (int b = 0; b < B; ++b) {
             const int u = win[g0 + b].utt;
             if (utt_lang[u] < 0) utt_lang[u] = lang[b];
             nwin[u]++;
+            const int i0 = (int)tok[u].size();
             for (int s2 = 0; s2 < rq.n_steps; ++s2) {
                 const int t = otok[(size_t)b * rq.n_steps + s2];
                 if (t < 0) break;
@@ -385,6 +421,8 @@ spt_status run_windows(spt_ctx* c, std::vector<Window>& win, const float* const*
                 if (t < eot) append_text(c, &text[u], t);
                 if (t == eot && !(rq.flags & SPT_IGNORE_EOT)) break;
             }
+            c->windows.push_back(spt_window_info{u, win[g0 + b].seek, 3000, i0, (int)tok[u].size() - i0, 0, 0.0f, NAN,
+                                                 nosp[b], 0});
         }
     }
     for (size_t u = 0; u < n_utt; ++u) {
@@ -401,7 +439,7 @@ spt_status run_windows(spt_ctx* c, std::vector<Window>& win, const float* const*
 
 extern "C" {
 
-const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice, qresident)"; }
+const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice, qresident, nospeech)"; }
 
 const char* spt_language_code(int32_t lang_id) { return spt::lang_code(lang_id); }
 
@@ -518,12 +556,13 @@ spt_status spt_ctx_info(const spt_ctx* ctx, spt_model_info* info) {
     return SPT_OK;
 }
 
-spt_status spt_transcribe_batch(spt_ctx* ctx, const float* const* pcm, const size_t* n_samples, size_t batch,
-                                const spt_infer_params* params, spt_result** out) {
+static spt_status transcribe_batch_impl(spt_ctx* ctx, const float* const* pcm, const size_t* n_samples, size_t batch,
+                                       const spt_infer_params* params, spt_result** out) {
     if (!ctx || !out || (batch && (!pcm || !n_samples))) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
     spt_infer_params dflt;
     spt_default_infer_params(&dflt);
     if (!params) params = &dflt;
+    if (spt_status s = begin_call(ctx, params)) return s;
     ctx->eng->reset_call_stats();
     if (full_mode(params)) {
         for (size_t u = 0; u < batch; ++u) {
@@ -569,7 +608,7 @@ spt_status spt_transcribe_batch(spt_ctx* ctx, const float* const* pcm, const siz
             std::vector<size_t> sn;
             for (size_t u : seek_loop) { sp.push_back(pcm[u]); sn.push_back(n_samples[u]); }
             std::vector<spt_result*> tmp(seek_loop.size(), nullptr);
-            s = run_full(ctx, sp.data(), sn.data(), sp.size(), params, tmp.data());
+            s = run_full(ctx, sp.data(), sn.data(), sp.size(), params, tmp.data(), nullptr, seek_loop.data());
             if (s != SPT_OK) {
                 for (size_t u = 0; u < batch; ++u) { spt_result_free(out[u]); out[u] = nullptr; }
                 return s;
@@ -581,12 +620,18 @@ spt_status spt_transcribe_batch(spt_ctx* ctx, const float* const* pcm, const siz
             std::vector<int> t; std::vector<float> a, b; std::string txt;
             out[u] = make_result(0, -1, &t, &a, &b, &txt);
         }
+        sort_windows(ctx);
         return SPT_OK;
     } catch (const std::exception& e) {
         // run_full may throw after run_windows filled out[]: no partial results with a failure status
         for (size_t u = 0; u < batch; ++u) { spt_result_free(out[u]); out[u] = nullptr; }
         return fail(ctx, classify(e), e.what());
     }
+}
+
+spt_status spt_transcribe_batch(spt_ctx* ctx, const float* const* pcm, const size_t* n_samples, size_t batch,
+                                const spt_infer_params* params, spt_result** out) {
+    return end_call(ctx, transcribe_batch_impl(ctx, pcm, n_samples, batch, params, out));
 }
 
 spt_status spt_transcribe(spt_ctx* ctx, const float* pcm16k, size_t n_samples, const spt_infer_params* params,
@@ -597,15 +642,21 @@ spt_status spt_transcribe(spt_ctx* ctx, const float* pcm16k, size_t n_samples, c
     return spt_transcribe_batch(ctx, &p, &n_samples, 1, params, out);
 }
 
-spt_status spt_transcribe_batch_device(spt_ctx* ctx, const float* pcm_dev, size_t stride, const size_t* n_samples,
-                                       size_t batch, const spt_infer_params* params, spt_result** out) {
+static spt_status transcribe_batch_device_impl(spt_ctx* ctx, const float* pcm_dev, size_t stride,
+                                              const size_t* n_samples, size_t batch, const spt_infer_params* params,
+                                              spt_result** out) {
     if (!ctx || !out || !pcm_dev || !n_samples || batch == 0) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
     if (batch > (size_t)ctx->eng->max_batch()) return fail(ctx, SPT_ERR_INVALID_ARG, "batch exceeds max_batch");
     if (stride < (size_t)kWindow) return fail(ctx, SPT_ERR_INVALID_ARG, "device stride must be >= 480000");
     spt_infer_params dflt;
     spt_default_infer_params(&dflt);
     if (!params) params = &dflt;  // the defaults are whisper_full's (timestamps on): unsupported here
+    if (spt_status s0 = begin_call(ctx, params)) return s0;
     ctx->eng->reset_call_stats();
+    if (skip_enabled(params))
+        return fail(ctx, SPT_ERR_INVALID_ARG,
+                    "device windows cannot evaluate no_speech_thold (a whisper_full rule); SPT_NO_SPEECH_PROB reports the "
+                    "probability");
     if (full_mode(params))
         return fail(ctx, SPT_ERR_UNSUPPORTED,
                     "device windows take the no-timestamp greedy protocol (SPT_NO_TIMESTAMPS, temperature_inc 0)");
@@ -626,8 +677,9 @@ spt_status spt_transcribe_batch_device(spt_ctx* ctx, const float* pcm_dev, size_
         Engine& e = *ctx->eng;
         const int B = (int)batch;
         std::vector<int> otok((size_t)B * rq.n_steps), lang(B, -1);
-        std::vector<float> o1((size_t)B * rq.n_steps), o2((size_t)B * rq.n_steps);
-        e.transcribe_device(pcm_dev, (int64_t)stride, ns.data(), B, rq, otok.data(), o1.data(), o2.data(), lang.data());
+        std::vector<float> o1((size_t)B * rq.n_steps), o2((size_t)B * rq.n_steps), nosp(B, NAN);
+        e.transcribe_device(pcm_dev, (int64_t)stride, ns.data(), B, rq, otok.data(), o1.data(), o2.data(), lang.data(),
+                            nullptr, rq.want_nosp ? nosp.data() : nullptr);
         const spt::Specials sp = spt::specials_for(e.dims().n_vocab);
         const int eot = sp.eot;
         for (int b = 0; b < B; ++b) {
@@ -642,11 +694,17 @@ spt_status spt_transcribe_batch_device(spt_ctx* ctx, const float* pcm_dev, size_
                 if (tk == eot && !(rq.flags & SPT_IGNORE_EOT)) break;
             }
             out[b] = make_result(1, lang_index(lang[b], sp), &t, &a, &c2, &txt);
+            ctx->windows.push_back(spt_window_info{b, 0, 3000, 0, (int)t.size(), 0, 0.0f, NAN, nosp[b], 0});
         }
         return SPT_OK;
     } catch (const std::exception& e) {
         return fail(ctx, classify(e), e.what());
     }
+}
+
+spt_status spt_transcribe_batch_device(spt_ctx* ctx, const float* pcm_dev, size_t stride, const size_t* n_samples,
+                                       size_t batch, const spt_infer_params* params, spt_result** out) {
+    return end_call(ctx, transcribe_batch_device_impl(ctx, pcm_dev, stride, n_samples, batch, params, out));
 }
 
 void spt_result_free(spt_result* r) {
@@ -694,6 +752,13 @@ spt_status spt_get_call_stats(const spt_ctx* ctx, spt_call_stats* s) {
     s->encoder_windows = c.encoder_windows;
     s->device_ms = c.device_ms; s->encoder_ms = c.encoder_ms; s->decode_ms = c.decode_ms;
     s->pd_passes = c.pd_passes; s->pd_fallbacks = c.pd_fallbacks;
+    return SPT_OK;
+}
+
+spt_status spt_get_window_info(const spt_ctx* ctx, spt_window_info* out, int32_t cap, int32_t* n) {
+    if (!ctx || !n || cap < 0 || (cap > 0 && !out)) return SPT_ERR_INVALID_ARG;
+    *n = (int32_t)ctx->windows.size();
+    for (int32_t i = 0; i < cap && i < *n; ++i) out[i] = ctx->windows[i];
     return SPT_OK;
 }
 
@@ -815,12 +880,14 @@ spt_status spt_set_alignment_heads(spt_ctx* ctx, const int32_t* layer_head, int3
     }
 }
 
-spt_status spt_transcribe_aligned_batch(spt_ctx* ctx, const float* const* pcm, const size_t* n_samples, size_t batch,
-                                        const spt_infer_params* params, spt_result** out, spt_alignment** align) {
+static spt_status transcribe_aligned_batch_impl(spt_ctx* ctx, const float* const* pcm, const size_t* n_samples,
+                                               size_t batch, const spt_infer_params* params, spt_result** out,
+                                               spt_alignment** align) {
     if (!ctx || !out || !align || (batch && (!pcm || !n_samples))) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
     spt_infer_params dflt;
     spt_default_infer_params(&dflt);
     if (!params) params = &dflt;
+    if (spt_status s = begin_call(ctx, params)) return s;
     ctx->eng->reset_call_stats();
     for (size_t u = 0; u < batch; ++u) {
         out[u] = nullptr;
@@ -836,6 +903,11 @@ spt_status spt_transcribe_aligned_batch(spt_ctx* ctx, const float* const* pcm, c
         }
         return fail(ctx, classify(e), e.what());
     }
+}
+
+spt_status spt_transcribe_aligned_batch(spt_ctx* ctx, const float* const* pcm, const size_t* n_samples, size_t batch,
+                                        const spt_infer_params* params, spt_result** out, spt_alignment** align) {
+    return end_call(ctx, transcribe_aligned_batch_impl(ctx, pcm, n_samples, batch, params, out, align));
 }
 
 spt_status spt_transcribe_aligned(spt_ctx* ctx, const float* pcm16k, size_t n_samples, const spt_infer_params* params,

@@ -3,6 +3,7 @@
 #include <exception>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "../../include/spittle_hip.h"
 #include "engine.h"
@@ -13,6 +14,7 @@ struct spt_ctx {
     std::unique_ptr<spt::Vocab> vocab;  // ggml models; synthetic models have none
     std::string spec;
     std::string err;
+    std::vector<spt_window_info> windows;  // the last spt_transcribe* call's windows (spt_get_window_info)
 };
 
 // record msg as the context's last error and return s

@@ -176,6 +176,39 @@ spt_status spt_debug_sample_beam(int32_t device, const float* logits, int32_t B,
     }
 }
 
+spt_status spt_debug_no_speech(int32_t device, const float* logits, int32_t B, int32_t n_vocab, int32_t ldl,
+                               int32_t nosp, float* prob, char* err, size_t errlen) {
+    if (!logits || !prob) {
+        set_err(err, errlen, "null argument");
+        return SPT_ERR_INVALID_ARG;
+    }
+    try {
+        if (B < 1 || B > 1024) throw std::runtime_error("debug_no_speech: need 1..1024 rows");
+        if (n_vocab < 1) throw std::runtime_error("debug_no_speech: empty vocabulary");
+        if (n_vocab > 53248) throw std::runtime_error("debug_no_speech: vocabulary above 53248 tokens");
+        if (ldl < n_vocab) throw std::runtime_error("debug_no_speech: ldl below n_vocab");
+        if (nosp < 0 || nosp >= n_vocab) throw std::runtime_error("debug_no_speech: nosp outside the vocabulary");
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return SPT_ERR_INVALID_ARG;
+    }
+    if (spt_status s = device_ok(device, err, errlen)) return s;
+    try {
+        const size_t nb = (size_t)B;
+        Scope sc(device);
+        const float* d_logits = sc.up(logits, nb * (size_t)ldl);
+        float* d_prob = sc.alloc<float>(nb);
+        float* d_stat = sc.alloc<float>(nb * spt::TS_CHUNKS * 2);
+        spt::dec_no_speech(d_logits, ldl, n_vocab, nosp, d_prob, d_stat, B, sc.st);
+        sc.down(prob, d_prob, nb);
+        sc.sync();
+        return SPT_OK;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return spt_classify(e);
+    }
+}
+
 spt_status spt_debug_sample_kv_gather(int32_t device, int32_t dtype, const float* src, float* dst,
                                       const int32_t* rows, int32_t L, int32_t B, int32_t H, int32_t ctx,
                                       int32_t pos0, char* err, size_t errlen) {

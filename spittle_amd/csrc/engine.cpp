@@ -687,6 +687,8 @@ void Engine::alloc_workspace() {
             g.cand_lp = (float*)c.take(B * 8 * 4);
             g.beam_tid = (int*)c.take(B * 4);
             g.kvrow = (int*)c.take(B * 4);
+            g.nosp = (float*)c.take(B * 4);
+            g.nosp_stat = (float*)c.take((int64_t)B * TS_CHUNKS * 2 * 4);
             g.xq_gran = (unsigned long long*)c.take(16 * d * 8);
         }
         zero_ = (float*)c.take(R * d * 4);  // never written: the "no pending slab" operand
@@ -1194,7 +1196,7 @@ void Engine::enqueue_head(DecGroup& g, int Tq, const DecodeRequest& rq, int out_
 }
 
 void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1, float* top2, int* lang_out,
-                        int* ts_state_out) {
+                        int* ts_state_out, float* nosp_out) {
     const int Tq = (int)rq.prompt.size();
     const int ctx = dm_.n_text_ctx;
     const int P = rq.row_prefix.empty() ? (int)rq.prefix.size() : (int)rq.row_prefix[0].size();
@@ -1401,6 +1403,12 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
             HIP_CHECK(hipMemcpyAsync(g.beam_step, beam_host_.data() + (size_t)g.B * 4, 4, hipMemcpyHostToDevice, g.st));
         }
         enqueue_decoder_pass(g, E, Tq_head, rq, out_cap);  // prompt pass produces token 0
+        // the no-speech probability: g.logits holds the last prompt token's raw logits until the next pass
+        if (rq.want_nosp && nosp_out) {
+            dec_no_speech(g.logits, dm_.n_vocab, dm_.n_vocab, sp.nosp, g.nosp, g.nosp_stat, g.B, g.st);
+            if (rq.beam_k > 0)  // a beam run returns before the read-backs below: decode()'s wait on st_, after g.ev, orders it
+                HIP_CHECK(hipMemcpyAsync(nosp_out + g.b0, g.nosp, (size_t)g.B * 4, hipMemcpyDeviceToHost, g.st));
+        }
     }
     if (rq.beam_k > 0) {  // beam search continues step by step from the host (beam_next)
         tm_.n_decode_passes = 1;
@@ -1474,13 +1482,15 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
         if (ts_state_out && rq.full)
             HIP_CHECK(hipMemcpyAsync(ts_state_out + (size_t)g->b0 * 4, g->ts_state, (size_t)g->B * 16,
                                      hipMemcpyDeviceToHost, g->st));
+        if (rq.want_nosp && nosp_out)
+            HIP_CHECK(hipMemcpyAsync(nosp_out + g->b0, g->nosp, (size_t)g->B * 4, hipMemcpyDeviceToHost, g->st));
         HIP_CHECK(hipEventRecord(g->ev, g->st));
         HIP_CHECK(hipStreamWaitEvent(st_, g->ev, 0));
     }
 }
 
 void Engine::decode(int B, const DecodeRequest& rq, int* tokens, float* top1, float* top2, int* lang_out,
-                    int* ts_state_out) {
+                    int* ts_state_out, float* nosp_out) {
     select();
     require_weights();
     // SPT_XQ_FUSE=0: the two-launch chain everywhere (read per call, applied when a pass is captured).  A
@@ -1499,7 +1509,7 @@ void Engine::decode(int B, const DecodeRequest& rq, int* tokens, float* top1, fl
     } xq_off{xq_on_};
     const int fused0 = cs_.xq_fused;
     HIP_CHECK(hipEventRecord(ev_[6], st_));  // the decode groups wait for the encoded windows here
-    run_decode(B, rq, tokens, top1, top2, lang_out, ts_state_out);
+    run_decode(B, rq, tokens, top1, top2, lang_out, ts_state_out, nosp_out);
     HIP_CHECK(hipEventRecord(ev_[7], st_));
     HIP_CHECK(hipStreamSynchronize(st_));
     HIP_CHECK(hipGetLastError());
@@ -1515,7 +1525,7 @@ void Engine::decode(int B, const DecodeRequest& rq, int* tokens, float* top1, fl
             xq_on_ = false;
             cs_.xq_fallbacks++;
             HIP_CHECK(hipEventRecord(ev_[6], st_));
-            run_decode(B, rq, tokens, top1, top2, lang_out, ts_state_out);
+            run_decode(B, rq, tokens, top1, top2, lang_out, ts_state_out, nosp_out);
             HIP_CHECK(hipEventRecord(ev_[7], st_));
             HIP_CHECK(hipStreamSynchronize(st_));
             HIP_CHECK(hipGetLastError());
@@ -1743,7 +1753,7 @@ void Engine::finish_call_timing() {
 
 void Engine::transcribe_device(const float* pcm_dev, int64_t stride, const int* n_samples, int B,
                                const DecodeRequest& rq, int* tokens, float* top1, float* top2, int* lang_out,
-                               int* ts_state_out) {
+                               int* ts_state_out, float* nosp_out) {
     if (B < 1 || B > max_batch_) throw std::runtime_error("batch exceeds the context's max_batch");
     for (int b = 0; b < B; ++b)
         if (n_samples[b] < 0 || n_samples[b] > 480000 || (int64_t)n_samples[b] > stride)
@@ -1752,7 +1762,7 @@ void Engine::transcribe_device(const float* pcm_dev, int64_t stride, const int* 
     std::vector<int> utt(B), seek(B, 0);
     for (int b = 0; b < B; ++b) utt[b] = b;
     encode_windows(utt.data(), seek.data(), B);
-    decode(B, rq, tokens, top1, top2, lang_out, ts_state_out);
+    decode(B, rq, tokens, top1, top2, lang_out, ts_state_out, nosp_out);
 }
 
 void Engine::transcribe_host(const float* const* pcm, const int* n_samples, int B, const DecodeRequest& rq,
@@ -1784,7 +1794,7 @@ void Engine::read_cands(int B, BeamCands* out) {
     memcpy(out->tid.data(), beam_rd_.data() + o_tid, (size_t)B * 4);
 }
 
-void Engine::beam_begin(int B, const DecodeRequest& rq, BeamCands* out, int* lang_out) {
+void Engine::beam_begin(int B, const DecodeRequest& rq, BeamCands* out, int* lang_out, float* nosp_out) {
     select();
     require_weights();
     if (rq.beam_k < 1 || rq.beam_k > 8) throw std::runtime_error("beam size must be in 1..8");
@@ -1811,7 +1821,7 @@ void Engine::beam_begin(int B, const DecodeRequest& rq, BeamCands* out, int* lan
     beam_B_ = B;
     beam_side_ = 0;  // the prompt pass writes the group's own cache
     std::vector<int> tok((size_t)B * rq.n_steps);
-    decode(B, rq, tok.data(), nullptr, nullptr, lang_out, nullptr);
+    decode(B, rq, tok.data(), nullptr, nullptr, lang_out, nullptr, nosp_out);
     read_cands(B, out);
 }
 

@@ -47,6 +47,9 @@ struct DecodeRequest {
     // decoders of one utterance: beam_size / best_of), so one workgroup reads a window's K/V once
     // for all of them.
     std::vector<int> kv_row;
+    // the no-speech probability of each row: one eager dec_no_speech on the raw logits of
+    // the last prompt token, after the pass that holds the first head; read back with the run's results
+    bool want_nosp = false;
 };
 
 // per-row beam candidates of one step (k <= 8 per row)
@@ -128,13 +131,15 @@ public:
     //    host [B][n_steps]; lang_out (optional, [B]): the language token each row was decoded with
     //    (-1: none); ts_state_out (optional, [B][4], whisper_full mode): has_ts, seek_delta,
     //    result_len, status (0 running, 1 completed, 2 failed) of each row's decoder
+    //    nosp_out (optional, [B], with rq.want_nosp): each row's no-speech probability
     void decode(int B, const DecodeRequest& rq, int* tokens, float* top1, float* top2, int* lang_out = nullptr,
-                int* ts_state_out = nullptr);
+                int* ts_state_out = nullptr, float* nosp_out = nullptr);
 
     // the three stages for B utterances that are one window each (seek 0), decoder row b on window b
     // pcm_dev: B windows at pcm_dev + b * stride (device memory)
     void transcribe_device(const float* pcm_dev, int64_t stride, const int* n_samples, int B, const DecodeRequest& rq,
-                           int* tokens, float* top1, float* top2, int* lang_out = nullptr, int* ts_state_out = nullptr);
+                           int* tokens, float* top1, float* top2, int* lang_out = nullptr, int* ts_state_out = nullptr,
+                           float* nosp_out = nullptr);
     void transcribe_host(const float* const* pcm, const int* n_samples, int B, const DecodeRequest& rq, int* tokens,
                          float* top1, float* top2, int* lang_out = nullptr, int* ts_state_out = nullptr);
 
@@ -143,7 +148,8 @@ public:
     // candidates; then one step per call: row b continues row src[b]'s sequence with tokens[b];
     // rowstate [B][4] = last token, previous token, has_ts, seek_delta; step = index of the token
     // being chosen
-    void beam_begin(int B, const DecodeRequest& rq, BeamCands* out, int* lang_out);
+    // nosp_out (optional, [B], with rq.want_nosp): read after the first candidate pass
+    void beam_begin(int B, const DecodeRequest& rq, BeamCands* out, int* lang_out, float* nosp_out = nullptr);
     void beam_next(const int* src, const int* tokens, const int* rowstate, int step, BeamCands* out);
 
     // ---- token alignment from the cross-attention
@@ -227,6 +233,7 @@ private:
         int *beam_row = nullptr, *beam_step = nullptr, *beam_src = nullptr;  // beam search
         int *cand_id = nullptr, *beam_tid = nullptr;
         float* cand_lp = nullptr;
+        float *nosp = nullptr, *nosp_stat = nullptr;  // [B] no-speech probabilities, [B][TS_CHUNKS][2] (dec_no_speech)
         int* kvrow = nullptr;         // [B] encoded window of each row (window map)
         int share = 0;                // rows per window of this call (0: identity, no map)
         unsigned long long* xq_gran = nullptr;  // [16][d] q granules of the fused cross-Q + cross-attention launch
@@ -252,7 +259,7 @@ private:
     void enqueue_encoder(int B);  // run_encoder, replayed from a per-B graph after the first call
     void run_cross_kv(int B);
     void run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1, float* top2, int* lang_out,
-                    int* ts_state_out);
+                    int* ts_state_out, float* nosp_out);
     // E: encoded windows (the cross K/V layout); g.share / g.kvrow: the rows' window map
     void enqueue_decoder_pass(DecGroup& g, int E, int Tq, const DecodeRequest& rq, int out_cap);
     float* enqueue_layers(DecGroup& g, int E, int Tq);

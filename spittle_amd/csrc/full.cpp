@@ -26,6 +26,7 @@ struct DecOut {                 // one decoder of one window
     int seek_delta = 0, result_len = 0, status = 0;  // status 1 completed, 2 failed
     bool failed = false;
     double avg = -INFINITY, score = -INFINITY;
+    float nosp = NAN;           // the row's no-speech probability (FullParams::no_speech_prob)
 };
 
 // whisper_sequence_score + the entropy check of whisper_full (length_penalty = -1: the score
@@ -82,6 +83,7 @@ void bookkeep(DecOut& d, int tok, int i, int seek, int seek_end, const FullParam
 void run_beam(Engine& e, const DecodeRequest& rq, int nj, int K, const std::vector<int>& seek,
               const std::vector<int>& seek_end, const FullParams& p, const Specials& sp, int n_max,
               std::vector<std::vector<DecOut>>* outs, std::vector<int>* lang) {
+    std::vector<float> nosp(rq.want_nosp ? nj * K : 0);
     const int B = nj * K;
     struct Dec {
         DecOut o;
@@ -92,7 +94,7 @@ void run_beam(Engine& e, const DecodeRequest& rq, int nj, int K, const std::vect
     for (Dec& d : dec) d.o.seek_delta = 3000;
     BeamCands c;
     lang->assign(B, -1);
-    e.beam_begin(B, rq, &c, lang->data());
+    e.beam_begin(B, rq, &c, lang->data(), rq.want_nosp ? nosp.data() : nullptr);
     struct Cand {
         int src;
         Dec d;
@@ -160,6 +162,9 @@ void run_beam(Engine& e, const DecodeRequest& rq, int nj, int K, const std::vect
         for (int dd = 0; dd < K; ++dd) {
             DecOut o = dec[j * K + dd].o;
             o.failed = o.status == 2;
+            // a decoder's sequence may have started on another row: every row of one utterance has the
+            // same prompt, hence the same probability
+            if (rq.want_nosp) o.nosp = nosp[j * K + dd];
             (*outs)[j].push_back(std::move(o));
         }
 }
@@ -220,6 +225,8 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
     // best_of sampled decoders per window; more than the context's rows run in further
     // sub-batches (beam search needs its rows together: run_full rejects beam_size > max_batch)
     const int ndec_hot = std::max(1, p.best_of);
+    const bool skip_on = p.no_speech_thold > 0.0f && p.no_speech_thold < 1.0f;
+    const bool want_nosp = p.no_speech_prob || skip_on;
 
     struct Utt {
         int seek = 0, seek_end = 0;
@@ -295,6 +302,7 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                     rq.extra_suppress = nst;
                     rq.blank_tok = blank;
                     rq.n_steps = std::min(n_max, dm.n_text_ctx + 1 - P - Tq);
+                    rq.want_nosp = want_nosp;
                     for (int j = 0; j < nj; ++j) {
                         const int u = grp[g0 + j];
                         for (int d = 0; d < nd; ++d) {
@@ -339,8 +347,9 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                     }
                     const int S = rq.n_steps;
                     std::vector<int> tok((size_t)B * S), lang(B, -1), state((size_t)B * 4);
-                    std::vector<float> plog((size_t)B * S), tid((size_t)B * S);
-                    e.decode(B, rq, tok.data(), plog.data(), tid.data(), lang.data(), state.data());
+                    std::vector<float> plog((size_t)B * S), tid((size_t)B * S), nosp(B, NAN);
+                    e.decode(B, rq, tok.data(), plog.data(), tid.data(), lang.data(), state.data(),
+                             want_nosp ? nosp.data() : nullptr);
                     for (int j = 0; j < nj; ++j) {
                         const int u = grp[g0 + j];
                         if (multi && us[u].lang < 0) {  // detected once, on the utterance's first window
@@ -362,6 +371,7 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                             o.result_len = state[r * 4 + 2];
                             o.status = state[r * 4 + 3];
                             o.failed = o.status == 2;
+                            o.nosp = nosp[r];
                             ds.push_back(std::move(o));
                         }
                     }
@@ -387,14 +397,19 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                 // the window's result (a failed decoder keeps every generated token)
                 FullResult& r = (*out)[u];
                 Utt& us_u = us[u];
-                const int len = bd.failed ? (int)bd.tok.size() : std::min<int>(bd.result_len, (int)bd.tok.size());
+                // the silence skip (whisper.cpp >= 1.7.3): the window contributes nothing but its count and
+                // its seek advance.  A NaN probability is never above the threshold.
+                const bool skip = skip_on && bd.nosp > p.no_speech_thold && bd.avg < p.logprob_thold;
+                const int len = skip ? 0 : bd.failed ? (int)bd.tok.size() : std::min<int>(bd.result_len, (int)bd.tok.size());
                 const int base = (int)r.tokens.size();
+                const int adv = bd.seek_delta > 0 ? bd.seek_delta : 3000;
+                r.windows.push_back(FullWindow{us_u.seek, adv, base, len, (int)it, t_cur, (float)bd.avg, bd.nosp, skip});
                 r.tokens.insert(r.tokens.end(), bd.tok.begin(), bd.tok.begin() + len);
                 r.plog.insert(r.plog.end(), bd.plog.begin(), bd.plog.begin() + len);
                 r.tid.insert(r.tid.end(), bd.tid.begin(), bd.tid.begin() + len);
                 r.n_windows++;
                 r.n_fallbacks += (int)it;
-                if (p.token_timestamps) {
+                if (p.token_timestamps && !skip) {
                     r.tok_t0.resize(r.tokens.size(), -1);
                     r.tok_t1.resize(r.tokens.size(), -1);
                     kept.push_back(Kept{u, base, len, us_u.seek});
@@ -403,7 +418,7 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                 const std::vector<int>& pf = prefix[u];
                 std::vector<int> past;
                 if (!pf.empty()) past.assign(pf.begin() + 1, pf.end());
-                for (int i = 0; i < bd.result_len && i < (int)bd.tok.size(); ++i) past.push_back(bd.tok[i]);
+                for (int i = 0; !skip && i < bd.result_len && i < (int)bd.tok.size(); ++i) past.push_back(bd.tok[i]);
                 us_u.past.swap(past);
                 // segments: split at timestamp tokens, text from the text tokens
                 auto text_of = [&](int t) { return vocab ? vocab->str(t) : "[" + std::to_string(t) + "]"; };
@@ -428,7 +443,7 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                         r.segments.push_back(FullSegment{t0, us_u.seek + bd.seek_delta, text, base + i0, len - i0});
                 }
                 // a decoder that made no progress would repeat the window forever: skip it whole
-                us_u.seek += bd.seek_delta > 0 ? bd.seek_delta : 3000;
+                us_u.seek += adv;
             }
             pending.swap(again);
         }

@@ -48,12 +48,28 @@ struct FullParams {  // whisper_full_params
     const int32_t* forced = nullptr;
     int n_forced = 0;
     bool ignore_eot = false;
+    // the no-speech probability and the silence skip.  no_speech_prob: compute each
+    // window's probability (FullWindow::no_speech_prob).  no_speech_thold in (0, 1): also drop a window
+    // whose probability > no_speech_thold and whose kept decoder's average log-probability <
+    // logprob_thold (whisper.cpp >= 1.7.3's rule; 0: off, as the reference's 1.7.1)
+    bool no_speech_prob = false;
+    float no_speech_thold = 0.0f;
 };
 
 struct FullSegment {
     int64_t t0, t1;   // 10 ms units (whisper_full_get_segment_t0 / t1)
     std::string text;
     int i0, n;        // its tokens in FullResult::tokens
+};
+
+struct FullWindow {       // one window of one utterance, in decode order
+    int seek, seek_delta;  // 10 ms frames; seek_delta: what the loop advanced by
+    int i0, n_tokens;      // its tokens in FullResult::tokens (none when skipped)
+    int n_fallbacks;       // index of the temperature kept
+    float temperature;
+    float avg_logprob;     // the kept decoder's
+    float no_speech_prob;  // NaN when not computed
+    bool skipped;
 };
 
 struct FullResult {
@@ -64,6 +80,7 @@ struct FullResult {
     std::vector<int64_t> tok_t0, tok_t1;
     std::vector<FullSegment> segments;
     std::string text;               // concatenated segment texts
+    std::vector<FullWindow> windows;
     int n_windows = 0;
     int n_fallbacks = 0;            // decodes repeated at a higher temperature (all windows)
     int lang_tok = -1;              // the language token decoded with (-1: English-only model)

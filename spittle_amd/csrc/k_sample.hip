@@ -704,4 +704,92 @@ void dec_finalize_ts(int dtype, const TsArgs& a, int B, hipStream_t st) {
     SPT_LAUNCH_CHECK();
 }
 
+// The no-speech probability of each row: softmax(raw logits)[nosp] -- no suppression
+// mask, no blank rule, no temperature -- over TS_CHUNKS workgroups per row as ts_stats_kernel: each
+// chunk writes its maximum and its exp sum relative to that maximum (NaN when the chunk holds a NaN or
+// +inf), and one thread per row merges the chunks in chunk order.  Every sum's order is a function of
+// n_vocab alone (thread: j ascending; wave: the xor butterfly; workgroup: waves ascending; row: chunks
+// ascending), so a row's bits do not depend on the batch or on its index in it.
+namespace {
+
+__global__ __launch_bounds__(TS_T) void no_speech_chunk_kernel(const float* __restrict__ logits, int ldl, int V,
+                                                               float* __restrict__ stat) {
+    __shared__ float s_m[TS_T / 64], s_s[TS_T / 64];
+    __shared__ int s_bad[TS_T / 64];
+    const int c = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int CS = (V + TS_CHUNKS - 1) / TS_CHUNKS, n0 = c * CS, n1 = min(V, n0 + CS);
+    const float* lg = logits + (size_t)b * ldl;
+    float lv[TS_J];
+#pragma unroll
+    for (int j = 0; j < TS_J; ++j) lv[j] = lg[min(n0 + tid + j * TS_T, V - 1)];  // columns < V only
+    float m = -INFINITY;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < TS_J; ++j) {
+        const bool in = n0 + tid + j * TS_T < n1;
+        bad = bad || (in && (lv[j] != lv[j] || lv[j] == INFINITY));
+        m = fmaxf(m, in ? lv[j] : -INFINITY);
+    }
+    m = wave_max(m);
+    const bool wbad = __any(bad);
+    if (lane == 0) { s_m[wv] = m; s_bad[wv] = wbad; }
+    __syncthreads();
+    m = s_m[0];
+    bool cbad = s_bad[0] != 0;
+    for (int w = 1; w < TS_T / 64; ++w) { m = fmaxf(m, s_m[w]); cbad = cbad || s_bad[w] != 0; }
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < TS_J; ++j) {
+        const bool in = n0 + tid + j * TS_T < n1;
+        const float e = expf(lv[j] - m);  // a -inf logit: 0
+        s += (in && m > -INFINITY) ? e : 0.0f;
+    }
+    s = wave_sum(s);
+    if (lane == 0) s_s[wv] = s;
+    __syncthreads();
+    if (tid == 0) {
+        float z = 0.0f;
+        for (int w = 0; w < TS_T / 64; ++w) z += s_s[w];
+        float* out = stat + ((size_t)b * TS_CHUNKS + c) * 2;
+        out[0] = m;
+        out[1] = cbad ? __int_as_float(0x7fc00000) : z;
+    }
+}
+
+__global__ __launch_bounds__(64) void no_speech_merge_kernel(const float* __restrict__ logits, int ldl, int nosp,
+                                                             const float* __restrict__ stat, float* __restrict__ prob,
+                                                             int B) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const float* sp = stat + (size_t)b * TS_CHUNKS * 2;
+    float cm[TS_CHUNKS], cs[TS_CHUNKS];
+#pragma unroll
+    for (int c = 0; c < TS_CHUNKS; ++c) { cm[c] = sp[2 * c]; cs[c] = sp[2 * c + 1]; }
+    const float ln = logits[(size_t)b * ldl + nosp];
+    float M = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < TS_CHUNKS; ++c) M = fmaxf(M, cm[c]);
+    float z = 0.0f;
+#pragma unroll
+    for (int c = 0; c < TS_CHUNKS; ++c) {
+        const float t = cs[c] * expf(cm[c] - M);
+        z += (cm[c] > -INFINITY || cs[c] != cs[c]) ? t : 0.0f;  // an all -inf chunk adds 0; a NaN chunk stays NaN
+    }
+    prob[b] = expf(ln - M) / z;
+}
+
+}  // namespace
+
+void dec_no_speech(const float* logits, int ldl, int n_vocab, int nosp, float* prob, float* stat, int B, hipStream_t st) {
+    if (n_vocab < 1 || n_vocab > TS_CHUNKS * TS_T * TS_J) throw std::runtime_error("no_speech: vocabulary above 53248 tokens");
+    if (ldl < n_vocab) throw std::runtime_error("no_speech: ldl below n_vocab");
+    if (nosp < 0 || nosp >= n_vocab) throw std::runtime_error("no_speech: nosp outside the vocabulary");
+    if (B < 1) throw std::runtime_error("no_speech: no rows");
+    if (!logits || !prob || !stat) throw std::runtime_error("no_speech: null buffer");
+    hipLaunchKernelGGL(no_speech_chunk_kernel, dim3(TS_CHUNKS, B), dim3(TS_T), 0, st, logits, ldl, n_vocab, stat);
+    SPT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(no_speech_merge_kernel, dim3((B + 63) / 64), dim3(64), 0, st, logits, ldl, nosp, stat, prob, B);
+    SPT_LAUNCH_CHECK();
+}
+
 }  // namespace spt

@@ -323,6 +323,10 @@ void dec_beam_topk(const BeamArgs& a, int B, hipStream_t st);
 // self-K/V cache rows for the next beam step: dst row b <- src row rows[b], positions < pos0
 void dec_kv_gather(int dtype, const void* src, void* dst, const int* rows, int L, int B, int H, int ctx,
                    const DecState* ds, hipStream_t st);
+// the no-speech probability of each row: softmax over the raw logits' columns < n_vocab (ldl >= n_vocab;
+// the pad is never read) at column nosp, f32, in an order fixed by n_vocab.  prob [B];
+// stat [B][TS_CHUNKS][2] per-chunk (maximum, exp sum).  A NaN or +inf in a row gives NaN.
+void dec_no_speech(const float* logits, int ldl, int n_vocab, int nosp, float* prob, float* stat, int B, hipStream_t st);
 // pos0 += n (after a prefill pass that produces no token)
 void dec_advance(DecState* ds, int n, hipStream_t st);
 

@@ -70,6 +70,12 @@ class WhisperInferenceParams:
     max_initial_ts: float = 1.0
     beam_size: int = 1
     seed: int = 0
+    # whisper_full_params.no_speech_thold (whisper.cpp >= 1.7.3): a window whose no-speech probability is
+    # above it and whose average log-probability is below logprob_thold is dropped.  On iff 0 < value < 1;
+    # 0 (the default, unlike whisper.cpp's 0.6) is off, as the reference's engine
+    no_speech_thold: float = 0.0
+    # report each window's no-speech probability (window_info()) without skipping
+    no_speech_prob: bool = False
     # benchmark / test hooks
     ignore_eot: bool = False
     forced_tokens: Optional[np.ndarray] = None  # [batch][n] teacher forcing
@@ -108,7 +114,11 @@ def _infer_params(p: Optional[WhisperInferenceParams], keep: list) -> L.InferPar
     ip.initial_prompt = p.initial_prompt.encode() if p.initial_prompt else None
     ip.flags = (L.SPT_SUPPRESS_BLANK if p.suppress_blank else 0) | \
                (L.SPT_NO_TIMESTAMPS if p.no_timestamps else 0) | (L.SPT_IGNORE_EOT if p.ignore_eot else 0) | \
-               (L.SPT_SUPPRESS_NST if p.suppress_non_speech_tokens else 0)
+               (L.SPT_SUPPRESS_NST if p.suppress_non_speech_tokens else 0) | \
+               (L.SPT_NO_SPEECH_PROB if p.no_speech_prob else 0)
+    if not float(p.no_speech_thold) >= 0.0:  # negative or NaN: refused here as the library refuses it
+        raise TranscriptionError(L.SPT_ERR_INVALID_ARG, "no_speech_thold must be >= 0 (0: off)")
+    ip.no_speech_thold = float(p.no_speech_thold)
     ip.max_new_tokens = int(p.max_new_tokens)
     ip.temperature = float(p.temperature)
     ip.beam_size = int(p.beam_size)
@@ -344,6 +354,17 @@ class WhisperEngine:
         t = L.CallStats()
         self._check(self._lib.spt_get_call_stats(self._ctx, C.byref(t)))
         return {k: getattr(t, k) for k, _ in t._fields_ if k != "reserved0"}
+
+    def window_info(self) -> list:
+        """One dict per window of the last transcribe* call, in decode order per utterance
+        (spt_get_window_info): utterance, seek, seek_delta, i0, n_tokens, n_fallbacks, temperature,
+        avg_logprob (NaN on the fast path), no_speech_prob (NaN when not computed), skipped."""
+        self._need()
+        n = C.c_int32(0)
+        self._check(self._lib.spt_get_window_info(self._ctx, None, 0, C.byref(n)))
+        buf = (L.WindowInfo * max(1, n.value))()
+        self._check(self._lib.spt_get_window_info(self._ctx, buf, n.value, C.byref(n)))
+        return [{k: getattr(buf[i], k) for k, _ in L.WindowInfo._fields_} for i in range(n.value)]
 
     def xq_stats(self) -> dict:
         """The last call's fused cross-Q + cross-attention launches and the engine calls it reran on the
