@@ -59,6 +59,11 @@ typedef enum {
 #define SPT_NO_SPEECH_PROB 16u  /* SPT_HAS_NO_SPEECH: compute and report each window's no-speech probability
                                    (spt_get_window_info) without skipping; an enabled no_speech_thold
                                    implies it.  The fast path stays the fast path */
+#define SPT_BLOCK_PREFILL  32u  /* SPT_HAS_BLOCK_PREFILL: a prompt prefix ([prev] + prompt tokens) of at least
+                                   P_min positions goes through the decoder layers in one block pass per
+                                   sequence slice (GEMMs + MFMA attention) instead of ceil(P / 4) chunked
+                                   passes.  Off by default; results differ from the chunked path in the low
+                                   bits (another accumulation order).  See spt_get_prefill_stats */
 
 typedef struct {
     int32_t dtype;        /* SPT_DTYPE_BF16 (default), SPT_DTYPE_F16 or SPT_DTYPE_F32: weights + activations at
@@ -99,7 +104,7 @@ typedef struct {
     int32_t translate;           /* task <|translate|> instead of <|transcribe|> */
     const char* initial_prompt;  /* jargon prompt text (src-tauri/src/jargon.rs:594); ggml models */
     uint32_t flags;              /* SPT_SUPPRESS_BLANK | SPT_NO_TIMESTAMPS | SPT_SUPPRESS_NST |
-                                    SPT_IGNORE_EOT | SPT_NO_SPEECH_PROB; default SPT_SUPPRESS_BLANK (whisper_full's
+                                    SPT_IGNORE_EOT | SPT_NO_SPEECH_PROB | SPT_BLOCK_PREFILL; default SPT_SUPPRESS_BLANK (whisper_full's
                                     defaults: timestamps on) */
     int32_t max_new_tokens;      /* fast path: generated tokens per 30 s window (<= 220);
                                     whisper_full path: whisper_full_params.max_tokens (0 = none) */
@@ -161,14 +166,15 @@ typedef struct {
     int32_t n_mels, d, n_head, n_enc, n_dec, n_vocab, n_audio_ctx, n_text_ctx;
     int32_t dtype, max_batch;
     int64_t weight_bytes;
-    int64_t workspace_bytes;
+    int64_t workspace_bytes;     /* the workspace arena, plus the block prefill workspaces allocated so far */
 } spt_model_info;
 
 /* per-phase device time of the last call, from HIP events on the engine stream; total_ms = the
  * sum of the phases */
 typedef struct {
     double mel_ms, encoder_ms, cross_kv_ms, decode_ms, total_ms, h2d_ms;
-    int32_t n_decode_passes;
+    int32_t n_decode_passes;  /* of the last engine run: prefix prefill passes (chunked or block), the prompt pass
+                                 and the decode steps */
     int32_t batch;
 } spt_timings;
 
@@ -227,7 +233,9 @@ spt_status spt_get_timings(const spt_ctx* ctx, spt_timings* t);
 typedef struct {
     int32_t engine_calls;     /* decoder runs (a prompt pass + its steps; ABI <= 10: each with its own
                                  mel + encoder + cross K/V) */
-    int32_t decoder_passes;   /* every decoder pass: prompt passes, decode steps, beam steps */
+    int32_t decoder_passes;   /* every decoder pass: prefix prefill passes (a chunked pass of <= 4 positions
+                                 and a block pass, SPT_BLOCK_PREFILL, count as one pass each), prompt passes,
+                                 decode steps, beam steps */
     int32_t beam_steps;       /* host-driven beam steps among them */
     int32_t encoder_windows;  /* ABI 11: 30 s windows encoded (conv stem + encoder + cross K/V): one
                                  per window, shared by every temperature fallback and decoder */
@@ -244,6 +252,21 @@ spt_status spt_get_call_stats(const spt_ctx* ctx, spt_call_stats* s);
  * the fused path) and the engine calls it reran on the two-launch chain because a fused launch's
  * bounded wait ran out (0 in normal operation).  Either pointer may be NULL. */
 spt_status spt_get_xq_stats(const spt_ctx* ctx, int32_t* fused_launches, int32_t* fallbacks);
+
+/* Block prefill of the prompt prefix (additive over ABI 14, announced by SPT_HAS_BLOCK_PREFILL and the
+ * word "blockprefill" in spt_version()).  With SPT_BLOCK_PREFILL in spt_infer_params.flags
+ * the prefix of a decode run ([prev] + the last <= 224 prompt tokens: initial_prompt, prompt_tokens, or
+ * whisper_full's prompt_past) of at least P_min = 17 positions (16 prompt tokens; the measured crossover) runs as one pass per slice of a decode
+ * group's sequences.  Honoured on the fast path and the whisper_full path (greedy, sampled, beam, the
+ * decode of spt_transcribe_aligned; its alignment replay stays chunked).  Ignored -- the prefix then
+ * takes the chunked passes, and the statistics say so -- on a context with SPT_MODEL_QUANT_RESIDENT
+ * weights resident (no dense decoder matrices) and for a prefix shorter than P_min.  The workspace
+ *  is allocated by the first flagged call that takes the block pass; SPT_ERR_OOM if that fails.
+ * spt_get_prefill_stats reports the last spt_transcribe* call: block passes run (one per decode-group
+ * slice), the prefix rows they carried, and chunked prefill passes of at most 4 positions.  Any pointer
+ * may be NULL; a call that fails leaves zeros. */
+#define SPT_HAS_BLOCK_PREFILL 1
+spt_status spt_get_prefill_stats(const spt_ctx* ctx, int32_t* block_passes, int32_t* block_rows, int32_t* chunk_passes);
 
 /* The no-speech probability and the silence skip (additive over ABI 14, announced by
  * SPT_HAS_NO_SPEECH and the word "nospeech" in spt_version()).  The probability of
@@ -417,6 +440,23 @@ spt_status spt_debug_attn_cross(int32_t device, int32_t dtype, int32_t mode, con
                                 const float* v, float pad_value, int32_t B, int32_t B_layout, int32_t b0, int32_t H,
                                 int32_t T_enc, int32_t Tq, int32_t splits, const int32_t* kvrow, int32_t share,
                                 float* out, float* part, char* err, size_t errlen);
+/* The block prefill's attention kernels alone (SPT_HAS_BLOCK_PREFILL), under the
+ * rules of the hooks above; every buffer a kernel writes starts with each byte 0xFF.
+ * Self: qkv [B*P][3*H*64] (q | k | v, head h at h*64; rounded to dtype) are positions 0..P-1 of B
+ * sequences.  cache [2][B][H][ctx][64] is in and out: uploaded rounded to dtype, rows 0..P-1 receive the
+ * K and V of qkv as the engine's cache store holds them (f16: clamped to +-65504), rows from P up come
+ * back as given.  Query t attends to keys 0..t -> out [B*P][H*64].  Refused: P < 1, P > ctx, H < 1,
+ * B or H outside 1..1024, a null buffer, a buffer above 2^26 elements, a dtype outside f32 / bf16 / f16. */
+spt_status spt_debug_attn_prefill_self(int32_t device, int32_t dtype, const float* qkv, float* cache, int32_t B, int32_t H,
+                                       int32_t ctx, int32_t P, float* out, char* err, size_t errlen);
+/* Cross: q [B*P][H*64]; k, v, pad_value, B_layout, b0, kvrow and share as spt_debug_attn_cross takes
+ * them; every one of the T_enc real keys, none of the padded ones -> out [B*P][H*64].  ctx bounds P as
+ * the engine's n_text_ctx does.  Also refused: T_enc < 1, b0 + B / share > B_layout, a window map entry
+ * outside the layout, share outside 1..8 or not dividing B, share > 1 without a map. */
+spt_status spt_debug_attn_prefill_cross(int32_t device, int32_t dtype, const float* q, const float* k, const float* v,
+                                        float pad_value, int32_t B, int32_t B_layout, int32_t b0, int32_t H,
+                                        int32_t T_enc, int32_t P, int32_t ctx, const int32_t* kvrow, int32_t share,
+                                        float* out, char* err, size_t errlen);
 /* The fused cross-Q + cross-attention launch alone (dec_xq_fused; additive over
  * ABI 14): x [B][1280] are the f32 residual rows, ln_w / ln_b [1280] the LayerNorm, wq [1280][1280] and
  * bias [1280] the cross-Q projection, k, v [B][20][T_enc][64] and pad_value as spt_debug_attn_cross takes

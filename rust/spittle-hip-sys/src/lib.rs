@@ -62,6 +62,8 @@ pub const SPT_IGNORE_EOT: u32 = 4;
 pub const SPT_SUPPRESS_NST: u32 = 8;
 /// report each window's no-speech probability without skipping (SPT_HAS_NO_SPEECH)
 pub const SPT_NO_SPEECH_PROB: u32 = 16;
+/// the prompt prefix in one block pass per sequence slice instead of chunks of 4 (SPT_HAS_BLOCK_PREFILL)
+pub const SPT_BLOCK_PREFILL: u32 = 32;
 
 pub const SPT_MODEL_WEIGHTS_EXTERNAL: u32 = 1;
 /// quantised decoder matrices of a ggml file stay resident in their blocks (SPT_HAS_QUANT_RESIDENT)
@@ -507,6 +509,43 @@ extern "C" {
     pub fn spt_get_call_stats(ctx: *const spt_ctx, s: *mut spt_call_stats) -> spt_status;
     // additive to ABI 14: fused cross-Q + cross-attention launches and chain reruns of the last call
     pub fn spt_get_xq_stats(ctx: *const spt_ctx, fused_launches: *mut i32, fallbacks: *mut i32) -> spt_status;
+    // block prefill of the prompt prefix (SPT_HAS_BLOCK_PREFILL, additive over ABI 14): the last call's
+    // block passes, the prefix rows they carried, and its chunked prefill passes
+    pub fn spt_get_prefill_stats(ctx: *const spt_ctx, block_passes: *mut i32, block_rows: *mut i32, chunk_passes: *mut i32) -> spt_status;
+    // the block prefill's attention kernels alone (cache: in and out)
+    pub fn spt_debug_attn_prefill_self(
+        device: i32,
+        dtype: i32,
+        qkv: *const f32,
+        cache: *mut f32,
+        B: i32,
+        H: i32,
+        ctx: i32,
+        P: i32,
+        out: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
+    pub fn spt_debug_attn_prefill_cross(
+        device: i32,
+        dtype: i32,
+        q: *const f32,
+        k: *const f32,
+        v: *const f32,
+        pad_value: f32,
+        B: i32,
+        B_layout: i32,
+        b0: i32,
+        H: i32,
+        T_enc: i32,
+        P: i32,
+        ctx: i32,
+        kvrow: *const i32,
+        share: i32,
+        out: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
     // the no-speech probability and the silence skip (SPT_HAS_NO_SPEECH, additive over ABI 14)
     pub fn spt_get_window_info(ctx: *const spt_ctx, out: *mut spt_window_info, cap: i32, n: *mut i32) -> spt_status;
     pub fn spt_debug_no_speech(
@@ -1187,6 +1226,8 @@ pub const SPT_HAS_ALIGN_KERNELS: c_int = 1;
 pub const SPT_HAS_TOKEN_TIMESTAMPS: c_int = 1;
 /// the no-speech probability, the silence skip and `spt_get_window_info` are present
 pub const SPT_HAS_NO_SPEECH: c_int = 1;
+/// `SPT_BLOCK_PREFILL`, `spt_get_prefill_stats` and the prefill attention hooks are present
+pub const SPT_HAS_BLOCK_PREFILL: c_int = 1;
 
 /// a text token's start and end (10 ms units), probability and index into `spt_result.tokens`
 #[repr(C)]

@@ -197,6 +197,18 @@ pub struct HipWhisperEngine {
     ctx: *mut sys::spt_ctx,
     no_speech_thold: f32,
     no_speech_prob: bool,
+    block_prefill: bool,
+}
+
+/// The last call's prefix prefill (`spt_get_prefill_stats`, `SPT_HAS_BLOCK_PREFILL`).
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct PrefillStats {
+    /// block passes run, one per decode-group slice
+    pub block_passes: i32,
+    /// prefix rows they carried
+    pub block_rows: i32,
+    /// chunked prefill passes of at most 4 positions
+    pub chunk_passes: i32,
 }
 
 /// One window of the last call (`spt_get_window_info`, `SPT_HAS_NO_SPEECH`).
@@ -226,7 +238,7 @@ unsafe impl Send for HipWhisperEngine {}
 
 impl HipWhisperEngine {
     pub fn new() -> Self {
-        Self { ctx: std::ptr::null_mut(), no_speech_thold: 0.0, no_speech_prob: false }
+        Self { ctx: std::ptr::null_mut(), no_speech_thold: 0.0, no_speech_prob: false, block_prefill: false }
     }
 
     fn last_error(&self) -> String {
@@ -251,10 +263,34 @@ impl HipWhisperEngine {
         self.no_speech_prob = report;
     }
 
+    /// `SPT_BLOCK_PREFILL` for the calls that follow: a prompt prefix (`initial_prompt`, or
+    /// whisper_full's `prompt_past` of a later window) of at least 17 positions (16 prompt tokens) runs as one block pass per
+    /// sequence slice instead of chunks of 4 positions.  Off by default; the low bits of the results
+    /// differ from the chunked path's.  Ignored by a model loaded with `load_model_quant_resident`.
+    pub fn set_block_prefill(&mut self, on: bool) {
+        self.block_prefill = on;
+    }
+
+    /// What the last transcribe call's prefix prefill ran.
+    pub fn prefill_stats(&self) -> Result<PrefillStats, Box<dyn Error>> {
+        self.need()?;
+        let (mut a, mut b, mut c) = (0i32, 0i32, 0i32);
+        // SAFETY: a live context and three valid out-pointers
+        let st = unsafe { sys::spt_get_prefill_stats(self.ctx, &mut a, &mut b, &mut c) };
+        if st != sys::SPT_OK {
+            return Err(status_error("prefill stats", st, self.last_error()));
+        }
+        Ok(PrefillStats { block_passes: a, block_rows: b, chunk_passes: c })
+    }
+
+    // the engine's per-call options (set_no_speech, set_block_prefill) into a request
     fn apply_no_speech(&self, rq: &mut Request) {
         rq.ip.no_speech_thold = self.no_speech_thold;
         if self.no_speech_prob {
             rq.ip.flags |= sys::SPT_NO_SPEECH_PROB;
+        }
+        if self.block_prefill {
+            rq.ip.flags |= sys::SPT_BLOCK_PREFILL;
         }
     }
 

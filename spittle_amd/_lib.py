@@ -17,6 +17,8 @@ STATUS_NAMES = {0: "OK", 1: "INVALID_ARG", 2: "LOAD", 3: "DEVICE", 4: "OOM", 5: 
 SPT_DTYPE_F32, SPT_DTYPE_BF16, SPT_DTYPE_F16, SPT_DTYPE_I8 = 0, 1, 2, 3
 SPT_SUPPRESS_BLANK, SPT_NO_TIMESTAMPS, SPT_IGNORE_EOT, SPT_SUPPRESS_NST = 1, 2, 4, 8
 SPT_NO_SPEECH_PROB = 16  # SPT_HAS_NO_SPEECH: report each window's no-speech probability without skipping
+SPT_BLOCK_PREFILL = 32   # SPT_HAS_BLOCK_PREFILL: the prompt prefix in one block pass per sequence slice
+SPT_HAS_BLOCK_PREFILL = 1
 
 # every symbol include/spittle_hip.h declares
 EXPORTS = [
@@ -78,6 +80,8 @@ EXPORTS = [
     "spt_debug_align_last", "spt_debug_align_stats",
     # the no-speech probability and the silence skip (SPT_HAS_NO_SPEECH)
     "spt_get_window_info", "spt_debug_no_speech",
+    # block prefill of the prompt prefix (SPT_HAS_BLOCK_PREFILL)
+    "spt_get_prefill_stats", "spt_debug_attn_prefill_self", "spt_debug_attn_prefill_cross",
 ]
 
 
@@ -371,6 +375,8 @@ def load():
     L.spt_get_timings.argtypes = [vp, C.POINTER(Timings)]
     L.spt_get_call_stats.argtypes = [vp, C.POINTER(CallStats)]
     L.spt_get_xq_stats.argtypes = [vp, ip, ip]
+    L.spt_get_prefill_stats.argtypes = [vp, ip, ip, ip]
+    L.spt_get_prefill_stats.restype = C.c_int
     L.spt_get_window_info.argtypes = [vp, C.POINTER(WindowInfo), C.c_int32, ip]
     L.spt_get_window_info.restype = C.c_int
     L.spt_debug_mel.argtypes = [vp, fp, C.c_size_t, fp]
@@ -537,7 +543,11 @@ def load():
                                        i32, fp, fp, C.c_char_p, C.c_size_t]
     L.spt_debug_xq_fused.argtypes = [i32, i32, fp, fp, fp, fp, fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, fp, fp,
                                      C.c_char_p, C.c_size_t]
-    for fn in ("spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross", "spt_debug_xq_fused"):
+    L.spt_debug_attn_prefill_self.argtypes = [i32, i32, fp, fp, i32, i32, i32, i32, fp, C.c_char_p, C.c_size_t]
+    L.spt_debug_attn_prefill_cross.argtypes = [i32, i32, fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32p,
+                                               i32, fp, C.c_char_p, C.c_size_t]
+    for fn in ("spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross", "spt_debug_xq_fused",
+               "spt_debug_attn_prefill_self", "spt_debug_attn_prefill_cross"):
         getattr(L, fn).restype = C.c_int
     # the GEMM tiles and LayerNorm kernels alone
     i64 = C.c_int64

@@ -107,7 +107,10 @@ spt_status begin_call(spt_ctx* c, const spt_infer_params* p) {
 // utterances before the seek-loop ones)
 // a call that fails reports no windows: the records are those of the last call that succeeded or none
 spt_status end_call(spt_ctx* c, spt_status s) {
-    if (c && s != SPT_OK) c->windows.clear();
+    if (c && s != SPT_OK) {
+        c->windows.clear();
+        if (c->eng) c->eng->clear_prefill_stats();  // spt_get_prefill_stats: a call that fails leaves zeros
+    }
     return s;
 }
 
@@ -161,8 +164,10 @@ spt_status build_request(spt_ctx* c, const spt_infer_params* p, spt::DecodeReque
     const int used = (int)(rq->prefix.size() + rq->prompt.size());
     if (used + n > dm.n_text_ctx + 1) n = dm.n_text_ctx + 1 - used;
     rq->n_steps = n;
-    rq->flags = p->flags & ~SPT_NO_SPEECH_PROB;  // not a decoding rule: the passes and their graphs are the same
+    // neither is a decoding rule: the passes and their graphs are the same
+    rq->flags = p->flags & ~(SPT_NO_SPEECH_PROB | SPT_BLOCK_PREFILL);
     rq->want_nosp = (p->flags & SPT_NO_SPEECH_PROB) != 0;
+    rq->block_prefill = (p->flags & SPT_BLOCK_PREFILL) != 0;
     rq->forced = p->forced_tokens;
     rq->n_forced = p->forced_tokens ? p->n_forced : 0;
     if (rq->n_forced < 0 || rq->n_forced > dm.n_text_ctx) return fail(c, SPT_ERR_INVALID_ARG, "n_forced out of range");
@@ -317,6 +322,7 @@ spt_status run_full(spt_ctx* c, const float* const* pcm, const size_t* n_samples
     }
     fp.ignore_eot = align && (p->flags & SPT_IGNORE_EOT) != 0;
     fp.no_speech_prob = (p->flags & SPT_NO_SPEECH_PROB) != 0;
+    fp.block_prefill = (p->flags & SPT_BLOCK_PREFILL) != 0;
     fp.no_speech_thold = skip_enabled(p) ? p->no_speech_thold : 0.0f;
     std::vector<const float*> ptr(batch);
     std::vector<int> ns(batch);
@@ -439,7 +445,7 @@ spt_status run_windows(spt_ctx* c, std::vector<Window>& win, const float* const*
 
 extern "C" {
 
-const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice, qresident, nospeech)"; }
+const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice, qresident, nospeech, blockprefill)"; }
 
 const char* spt_language_code(int32_t lang_id) { return spt::lang_code(lang_id); }
 
@@ -767,6 +773,15 @@ spt_status spt_get_xq_stats(const spt_ctx* ctx, int32_t* fused_launches, int32_t
     const spt::CallStats& c = ctx->eng->call_stats();
     if (fused_launches) *fused_launches = c.xq_fused;
     if (fallbacks) *fallbacks = c.xq_fallbacks;
+    return SPT_OK;
+}
+
+spt_status spt_get_prefill_stats(const spt_ctx* ctx, int32_t* block_passes, int32_t* block_rows, int32_t* chunk_passes) {
+    if (!ctx) return SPT_ERR_INVALID_ARG;
+    const spt::CallStats& c = ctx->eng->call_stats();
+    if (block_passes) *block_passes = c.block_passes;
+    if (block_rows) *block_rows = c.block_rows;
+    if (chunk_passes) *chunk_passes = c.chunk_passes;
     return SPT_OK;
 }
 

@@ -16,6 +16,7 @@
 #include "capi_internal.h"
 #include "common.h"
 #include "kernels.h"
+#include "prefill_host.h"
 
 namespace {
 
@@ -260,6 +261,74 @@ spt_status spt_debug_xq_fused(int32_t device, int32_t dtype, const float* x, con
             set_err(err, errlen, "debug_xq_fused: a consumer's wait for q ran out");
             return SPT_ERR_DEVICE;
         }
+        return SPT_OK;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return spt_classify(e);
+    }
+}
+
+// The block prefill's attention kernels alone (k_prefill.hip).  What they refuse is
+// prefill_host.h's, decided before the device is looked for.
+spt_status spt_debug_attn_prefill_self(int32_t device, int32_t dtype, const float* qkv, float* cache, int32_t B, int32_t H,
+                                       int32_t ctx, int32_t P, float* out, char* err, size_t errlen) {
+    const std::string why = spt::prefill_self_refusal(dtype, qkv, cache, out, B, H, ctx, P);
+    if (!why.empty()) {
+        set_err(err, errlen, why);
+        return SPT_ERR_INVALID_ARG;
+    }
+    if (spt_status s = device_ok(device, err, errlen)) return s;
+    try {
+        const size_t rows = (size_t)B * P, d = (size_t)H * 64, nc = (size_t)2 * B * H * ctx * 64;
+        const size_t esz = (size_t)spt::dtype_size(dtype);
+        std::vector<uint16_t> q16, c16;
+        Scope sc(device);
+        const void* d_qkv = up_as(sc, dtype, qkv, rows * 3 * d, q16);
+        void* d_c = const_cast<void*>(up_as(sc, dtype, cache, nc, c16));
+        void* d_out = sc.out<char>(rows * d * esz);
+        spt::dec_prefill_self_attn(dtype, d_qkv, d_c, B, B, H, ctx, P, d_out, sc.st);
+        down_f32(sc, dtype, d_out, out, rows * d);
+        down_f32(sc, dtype, d_c, cache, nc);
+        sc.sync();
+        return SPT_OK;
+    } catch (const std::exception& e) {
+        set_err(err, errlen, e.what());
+        return spt_classify(e);
+    }
+}
+
+spt_status spt_debug_attn_prefill_cross(int32_t device, int32_t dtype, const float* q, const float* k, const float* v,
+                                        float pad_value, int32_t B, int32_t B_layout, int32_t b0, int32_t H,
+                                        int32_t T_enc, int32_t P, int32_t ctx, const int32_t* kvrow, int32_t share,
+                                        float* out, char* err, size_t errlen) {
+    const std::string why = spt::prefill_cross_refusal(dtype, q, k, v, out, B, B_layout, b0, H, T_enc, P, ctx, kvrow, share);
+    if (!why.empty()) {
+        set_err(err, errlen, why);
+        return SPT_ERR_INVALID_ARG;
+    }
+    if (spt_status s = device_ok(device, err, errlen)) return s;
+    try {
+        // the layer as the K/V GEMM's epilogue writes it, as spt_debug_attn_cross lays it out
+        const size_t n_kv = (size_t)spt::kv_layer_elems(B_layout, H, T_enc);
+        std::vector<float> lay(n_kv, pad_value);
+        for (int kvi = 0; kvi < 2; ++kvi) {
+            const float* src = kvi ? v : k;
+            for (int b = 0; b < B_layout; ++b)
+                for (int h = 0; h < H; ++h)
+                    for (int t = 0; t < T_enc; ++t)
+                        memcpy(lay.data() + spt::kv_offset(0, kvi, b, h, t, 0, B_layout, H, T_enc),
+                               src + (((size_t)b * H + h) * T_enc + t) * 64, 64 * sizeof(float));
+        }
+        const size_t nq = (size_t)B * P * H * 64, esz = (size_t)spt::dtype_size(dtype);
+        std::vector<uint16_t> q16, kv16;
+        Scope sc(device);
+        const void* d_q = up_as(sc, dtype, q, nq, q16);
+        const char* d_kv = (const char*)up_as(sc, dtype, lay.data(), n_kv, kv16) + (size_t)b0 * H * 4096 * esz;
+        const int* d_map = kvrow ? sc.up(kvrow, (size_t)B) : nullptr;
+        void* d_out = sc.out<char>(nq * esz);
+        spt::dec_prefill_cross_attn(dtype, d_q, d_kv, B, B_layout, H, T_enc, P, d_out, sc.st, d_map, share);
+        down_f32(sc, dtype, d_out, out, nq);
+        sc.sync();
         return SPT_OK;
     } catch (const std::exception& e) {
         set_err(err, errlen, e.what());

@@ -10,6 +10,7 @@
 #include "engine.h"
 #include "ggml_file.h"
 #include "ggml_qpack.h"
+#include "prefill_host.h"
 
 #include <cstdio>
 
@@ -102,6 +103,14 @@ Engine::Engine(const ModelDims& dm, int dtype, int device, int max_batch, uint64
     if ((3 * cp_ * esz_) % 128) cp_ = ((dm_.n_mels + 127) / 128) * 128;
     if (const char* g = getenv("SPT_DECODE_GROUPS")) n_groups_ = std::max(1, std::min(4, atoi(g)));
     if (const char* v = getenv("SPT_XATTN_SPLIT")) xsplit_ = std::max(1, std::min(4, atoi(v)));
+    // block prefill: P_min and the workspace's row cap are fixed per engine, read here once
+    // (SPT_BLOCK_PREFILL_MIN: measurements of the crossover; SPT_BLOCK_PREFILL_ROWS: tests of the slicing)
+    quant_flag_ = quant_resident;
+    pf_min_ = kPrefillMinDefault;
+    if (const char* v = getenv("SPT_BLOCK_PREFILL_MIN")) pf_min_ = std::max(1, atoi(v));
+    int pf_cap = kPrefillRowCap;
+    if (const char* v = getenv("SPT_BLOCK_PREFILL_ROWS")) pf_cap = std::max(1, atoi(v));
+    pf_rows_ = prefill_ws_rows(pf_cap, dm_.n_text_ctx);
     // cross-attention key split: fixed per engine (never per batch).  The fc2 K split (2; r1
     // exp14 measured 2 slightly faster per layer than 4: the next QKV LayerNorm prologue sums
     // fewer slabs) is fixed per engine too; the pending-slab count a LayerNorm prologue sums is
@@ -156,6 +165,8 @@ void Engine::release() {
     if (st_) (void)hipStreamSynchronize(st_);
     for (auto& g : groups_) {
         if (g.st) (void)hipStreamSynchronize(g.st);
+        if (g.pf_ws) (void)hipFree(g.pf_ws);
+        g.pf_ws = nullptr;
         for (auto& kv : g.graphs) (void)hipGraphExecDestroy(kv.second.exec);
         if (g.ev) (void)hipEventDestroy(g.ev);
         if (g.st) (void)hipStreamDestroy(g.st);
@@ -1130,6 +1141,84 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
     return xc;
 }
 
+// The block prefill workspace of one decode group: allocated once, outside the arenas, freed by release().
+void Engine::ensure_prefill_ws(DecGroup& g) {
+    if (g.pf_ws) return;
+    const int64_t d = dm_.d, r = pf_rows_;
+    const int64_t bytes = prefill_ws_bytes(pf_rows_, dm_.d, esz_);
+    void* p = nullptr;
+    if (hipMalloc(&p, (size_t)bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        throw std::runtime_error("out of device memory for the block prefill workspace (" + std::to_string(bytes) + " B)");
+    }
+    g.pf_ws = (char*)p;
+    pf_bytes_ += bytes;
+    Carver c{g.pf_ws};  // the arrays in prefill_ws_bytes' order, each a multiple of 256 bytes
+    g.pf_tok = (int*)c.take(r * 4);
+    g.pf_x = (float*)c.take(r * d * 4);
+    g.pf_xn = c.take(r * d * esz_);
+    g.pf_qkv = c.take(r * 3 * d * esz_);
+    g.pf_q = c.take(r * d * esz_);
+    g.pf_ao = c.take(r * d * esz_);
+    g.pf_ff = c.take(r * 4 * d * esz_);
+    if (c.off > bytes) throw std::runtime_error("block prefill workspace: carving and prefill_ws_bytes disagree");
+}
+
+// The prompt prefix of every sequence of the group through the decoder layers, one pass per slice of
+// whole sequences: LayerNorm, GEMMs on the dense weights (the residual adds in place, so no
+// pending slabs cross a layer), and the two prefill attention kernels; the self K/V of positions
+// 0..P-1 land in the group's cache as the one-row path would store them.  No logits.  A sequence's rows
+// depend on no other sequence's, and every GEMM runs one fixed tile whatever M is, so the slicing and
+// the batch change no bit.  Returns the passes (slices) enqueued.
+int Engine::enqueue_prefix_block(DecGroup& g, int E, int P, const int* host_tok) {
+    const int d = dm_.d, H = dm_.n_head, ctx = dm_.n_text_ctx, T = dm_.n_audio_ctx;
+    if (P < 1 || P > ctx) throw std::runtime_error("block prefill: prefix length out of range");
+    for (const DecL& e : dec_)
+        if (e.qkv_q || e.so_q || e.cq_q || e.co_q || e.fc1_q || e.fc2_q)
+            throw std::runtime_error("block prefill: a decoder matrix is resident in packed blocks");
+    if (tok_q_) throw std::runtime_error("block prefill: the token embedding is resident in packed blocks");
+    ensure_prefill_ws(g);
+    const int per = prefill_slice_seqs(g.B, P, pf_rows_);
+    if (per < 1) throw std::runtime_error("block prefill: a prefix exceeds the workspace rows");
+    const int64_t self_layer = (int64_t)2 * g.B * H * ctx * 64, cross_layer = kv_layer_elems(E, H, T);
+    const bool mapped = g.share > 0;
+    hipStream_t st = g.st;
+    constexpr int kTile = 5;  // the 64 x 64 GEMM tile for every product: a row's bits do not depend on M
+    auto gemm = [&](int epi, const void* A, int K, const void* W, const float* bias, void* C, int N, int M) {
+        GemmArgs a{};
+        a.A = A; a.lda = K; a.W = W; a.ldw = K; a.M = M; a.N = N; a.K = K; a.bias = bias; a.C = C; a.ldc = N;
+        gemm_nt_variant(dt_, epi, a, 1, kTile, st);
+    };
+    int slices = 0;
+    for (int s0 = 0; s0 < g.B; s0 += per, ++slices) {
+        const int n = std::min(per, g.B - s0), R = n * P;
+        HIP_CHECK(hipMemcpyAsync(g.pf_tok, host_tok + (size_t)s0 * P, (size_t)R * 4, hipMemcpyHostToDevice, st));
+        dec_embed(dt_, g.pf_tok, R, P, d, tok_emb_, 0, dec_pos_, g.ds, g.pf_x, st);
+        // the rows' windows: identity rows read window g.b0 + s0 + b; mapped rows their own entry of the
+        // map (every row of a run holds the run's window, run_decode checks it)
+        const int* kvrow = mapped ? g.kvrow + s0 : nullptr;
+        for (int l = 0; l < dm_.n_dec; ++l) {
+            const DecL& e = dec_[l];
+            void* skv_l = (char*)g.skv + (self_layer * l + (int64_t)s0 * H * ctx * 64) * esz_;
+            const void* ckv_l = (const char*)ckv_ + (cross_layer * l + (mapped ? 0 : (int64_t)(g.b0 + s0) * H * 4096)) * esz_;
+            layernorm(dt_, g.pf_x, R, d, e.ln1_w, e.ln1_b, g.pf_xn, st);
+            gemm(EPI_BIAS, g.pf_xn, d, e.qkv_w, e.qkv_b, g.pf_qkv, 3 * d, R);
+            dec_prefill_self_attn(dt_, g.pf_qkv, skv_l, n, g.B, H, ctx, P, g.pf_ao, st);
+            gemm(EPI_BIAS_RESID, g.pf_ao, d, e.so_w, e.so_b, g.pf_x, d, R);
+            layernorm(dt_, g.pf_x, R, d, e.ln2_w, e.ln2_b, g.pf_xn, st);
+            gemm(EPI_BIAS, g.pf_xn, d, e.cq_w, e.cq_b, g.pf_q, d, R);
+            dec_prefill_cross_attn(dt_, g.pf_q, ckv_l, n, E, H, T, P, g.pf_ao, st, kvrow, 1);
+            gemm(EPI_BIAS_RESID, g.pf_ao, d, e.co_w, e.co_b, g.pf_x, d, R);
+            layernorm(dt_, g.pf_x, R, d, e.ln3_w, e.ln3_b, g.pf_xn, st);
+            gemm(EPI_BIAS_GELU, g.pf_xn, d, e.fc1_w, e.fc1_b, g.pf_ff, 4 * d, R);
+            gemm(EPI_BIAS_RESID, g.pf_ff, 4 * d, e.fc2_w, e.fc2_b, g.pf_x, d, R);
+        }
+    }
+    cs_.block_passes += slices;
+    cs_.block_rows += g.B * P;
+    return slices;
+}
+
 void Engine::ln_source(GemvArgs& a, float* xc, float* pend, int np, int64_t slab) const {
     // x + p0 + p1 + ...; with the residual folded into slab 0 the sum starts at slab 0 (the same
     // additions in the same order: bitwise the same rows)
@@ -1372,6 +1461,9 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
     }
     if (lang_out)
         for (int b = 0; b < B; ++b) lang_out[b] = lang[b] >= 0 ? lang[b] : (Tq >= 3 ? rq.prompt[1] : -1);
+    // prefix prefill passes, counted as the steps are: once for the groups that run side by side (the
+    // first group is never the smallest)
+    int prefill_passes = 0;
     for (DecGroup* gp : act) {
         DecGroup& g = *gp;
         reset_outputs(g);
@@ -1379,12 +1471,25 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
         // sequence through the decoder layers only (no logits), positions 0..P-1
         const bool rows = !rq.row_prefix.empty();
         const int P = rows ? (int)rq.row_prefix[0].size() : (int)rq.prefix.size();
-        for (int c0 = 0; c0 < P; c0 += cmax) {
-            const int n = std::min(cmax, P - c0);
-            upload_tokens(g, [&](int b, int t) { return rows ? rq.row_prefix[b][c0 + t] : rq.prefix[c0 + t]; }, n);
-            dec_embed(dt_, g.tok_in, g.B * n, n, dm_.d, tok_emb_, tok_q_, dec_pos_, g.ds, g.dx, g.st);
-            enqueue_layers(g, E, n);
-            dec_advance(g.ds, n, g.st);
+        if (prefill_takes_block(rq.block_prefill, quant_flag_, P, pf_min_)) {
+            // SPT_BLOCK_PREFILL: the whole prefix in one pass per slice of the group's sequences
+            int* h = g.host_tok.data() + g.host_used;
+            for (int b = 0; b < g.B; ++b)
+                for (int t = 0; t < P; ++t) h[b * P + t] = rows ? rq.row_prefix[g.b0 + b][t] : rq.prefix[t];
+            g.host_used += (size_t)g.B * P;
+            const int slices = enqueue_prefix_block(g, E, P, h);
+            dec_advance(g.ds, P, g.st);
+            if (gp == act.front()) prefill_passes += slices;
+        } else {
+            for (int c0 = 0; c0 < P; c0 += cmax) {
+                const int n = std::min(cmax, P - c0);
+                upload_tokens(g, [&](int b, int t) { return rows ? rq.row_prefix[b][c0 + t] : rq.prefix[c0 + t]; }, n);
+                dec_embed(dt_, g.tok_in, g.B * n, n, dm_.d, tok_emb_, tok_q_, dec_pos_, g.ds, g.dx, g.st);
+                enqueue_layers(g, E, n);
+                dec_advance(g.ds, n, g.st);
+                if (gp == act.front()) ++prefill_passes;  // the groups run side by side: counted once
+                ++cs_.chunk_passes;
+            }
         }
         auto prompt_tok = [&](int b, int t) { return (t == 1 && lang[b] >= 0) ? lang[b] : rq.prompt[t]; };
         for (int c0 = 0; c0 < Tq - Tq_head; c0 += cmax) {  // only when Bg * Tq > max_rows_
@@ -1411,14 +1516,14 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
         }
     }
     if (rq.beam_k > 0) {  // beam search continues step by step from the host (beam_next)
-        tm_.n_decode_passes = 1;
+        tm_.n_decode_passes = 1 + prefill_passes;
         for (DecGroup* g : act) {
             HIP_CHECK(hipEventRecord(g->ev, g->st));
             HIP_CHECK(hipStreamWaitEvent(st_, g->ev, 0));
         }
         return;
     }
-    int passes = 1;
+    int passes = 1 + prefill_passes;
     static const bool no_graph = getenv("SPT_NO_GRAPH") != nullptr;  // eager passes (profilers, debugging)
     static const bool sync_debug = getenv("SPT_DEBUG_SYNC") != nullptr;  // per-pass sync + state check
     if (rq.n_steps > 1 && no_graph) {

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "prefill_host.h"
 #include "vocab.h"
 
 namespace spt {
@@ -50,6 +51,9 @@ struct DecodeRequest {
     // the no-speech probability of each row: one eager dec_no_speech on the raw logits of
     // the last prompt token, after the pass that holds the first head; read back with the run's results
     bool want_nosp = false;
+    // SPT_BLOCK_PREFILL: a prefix of at least P_min positions runs as block passes; not a
+    // decoding rule, so not among `flags` (the steps' graphs are the same)
+    bool block_prefill = false;
 };
 
 // per-row beam candidates of one step (k <= 8 per row)
@@ -72,6 +76,9 @@ struct CallStats {
     int pd_fallbacks = 0;
     int xq_fused = 0;      // fused cross-Q + cross-attention launches (dec_xq_fused) the call ran
     int xq_fallbacks = 0;  // engine calls rerun on the two-launch chain after a consumer gave up waiting
+    // prefix prefill (spt_get_prefill_stats): block passes (one per decode-group slice), the prefix rows
+    // they carried, and chunked passes of <= 4 positions; all of them are among decoder_passes
+    int block_passes = 0, block_rows = 0, chunk_passes = 0;
     double device_ms = 0, encoder_ms = 0, decode_ms = 0;
 };
 
@@ -109,10 +116,12 @@ public:
     void* weight_arena() const { return warena_; }
     int device() const { return dev_; }
     void commit_weights();
-    int64_t workspace_bytes() const { return abytes_; }
+    // the workspace arena plus the block prefill workspaces allocated so far
+    int64_t workspace_bytes() const { return abytes_ + pf_bytes_; }
     const Timings& timings() const { return tm_; }
     const CallStats& call_stats() const { return cs_; }
     void reset_call_stats() { cs_ = CallStats(); }
+    void clear_prefill_stats() { cs_.block_passes = cs_.block_rows = cs_.chunk_passes = 0; }
 
     // ---- staged calls: utterances -> encoder windows -> decoder rows (whisper.cpp whisper_full:
     // whisper_pcm_to_mel once per input, whisper_encode_internal once per window at `seek`, then
@@ -237,6 +246,12 @@ private:
         int* kvrow = nullptr;         // [B] encoded window of each row (window map)
         int share = 0;                // rows per window of this call (0: identity, no map)
         unsigned long long* xq_gran = nullptr;  // [16][d] q granules of the fused cross-Q + cross-attention launch
+        // block prefill workspace (outside the arenas, allocated by the group's first block pass): one
+        // allocation carved into tok [rows], x f32 [rows][d], xn, qkv [rows][3 d], q, ao, ff [rows][4 d]
+        char* pf_ws = nullptr;
+        int* pf_tok = nullptr;
+        float* pf_x = nullptr;
+        void *pf_xn = nullptr, *pf_qkv = nullptr, *pf_q = nullptr, *pf_ao = nullptr, *pf_ff = nullptr;
         std::map<GraphKey, PassGraph> graphs;
         std::vector<int> host_tok;    // host sources of the call's token uploads
         size_t host_used = 0;
@@ -263,6 +278,14 @@ private:
     // E: encoded windows (the cross K/V layout); g.share / g.kvrow: the rows' window map
     void enqueue_decoder_pass(DecGroup& g, int E, int Tq, const DecodeRequest& rq, int out_cap);
     float* enqueue_layers(DecGroup& g, int E, int Tq);
+    // the block prefill of the group's sequences, P positions each, host_tok [g.B][P] their
+    // tokens (alive until the stream has read them): one pass per slice of whole sequences that fits the
+    // workspace.  The group's step state is at position 0 and is not advanced here.
+    int enqueue_prefix_block(DecGroup& g, int E, int P, const int* host_tok);
+    void ensure_prefill_ws(DecGroup& g);
+    int pf_min_ = kPrefillMinDefault, pf_rows_ = 0;       // read once, in the constructor (SPT_BLOCK_PREFILL_MIN / _ROWS)
+    int64_t pf_bytes_ = 0;
+    bool quant_flag_ = false;            // created with SPT_MODEL_QUANT_RESIDENT: the block pass is not taken
     void enqueue_head(DecGroup& g, int Tq, const DecodeRequest& rq, int out_cap, float* xc, const uint32_t* sup,
                       bool blank);
 

@@ -303,6 +303,7 @@ void whisper_full_batch(Engine& e, const Vocab* vocab, const std::vector<const f
                     rq.blank_tok = blank;
                     rq.n_steps = std::min(n_max, dm.n_text_ctx + 1 - P - Tq);
                     rq.want_nosp = want_nosp;
+                    rq.block_prefill = p.block_prefill;
                     for (int j = 0; j < nj; ++j) {
                         const int u = grp[g0 + j];
                         for (int d = 0; d < nd; ++d) {

@@ -53,6 +53,7 @@ struct FullParams {  // whisper_full_params
     // whose probability > no_speech_thold and whose kept decoder's average log-probability <
     // logprob_thold (whisper.cpp >= 1.7.3's rule; 0: off, as the reference's 1.7.1)
     bool no_speech_prob = false;
+    bool block_prefill = false;  // SPT_BLOCK_PREFILL: every decode run's prefix as block passes
     float no_speech_thold = 0.0f;
 };
 

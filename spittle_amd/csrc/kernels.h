@@ -330,6 +330,22 @@ void dec_no_speech(const float* logits, int ldl, int n_vocab, int nosp, float* p
 // pos0 += n (after a prefill pass that produces no token)
 void dec_advance(DecState* ds, int n, hipStream_t st);
 
+// ------------------------------------------------------------------ block prefill attention (k_prefill.hip)
+// Positions 0..P-1 of each of B sequences in one launch (MFMA; 128 queries per workgroup, 64-key tiles).
+// qkv [B*P][3*H*64] as the QKV GEMM stores it.  The K and V rows go into the self cache
+// [2][cache_B][H][ctx][64] (cache: at the first of the B sequences) at positions 0..P-1 through
+// to_cache (the f16 clamp), and query t attends to keys 0..t as stored -> out [B*P][H*64].  Cache rows
+// from P up are neither read nor written.
+void dec_prefill_self_attn(int dtype, const void* qkv, void* cache, int B, int cache_B, int H, int ctx, int P, void* out,
+                           hipStream_t st);
+// q [B*P][H*64] over all T_enc real keys of one layer of the cross K/V cache (kv, B_layout, kvrow and
+// share as dec_cross_attn takes them) -> out [B*P][H*64]; the keys that pad the last 32-key block are
+// never admitted, whatever they hold
+void dec_prefill_cross_attn(int dtype, const void* q, const void* kv, int B, int B_layout, int H, int T_enc, int P,
+                            void* out, hipStream_t st, const int* kvrow = nullptr, int share = 1);
+// what both launchers refuse on their shared arguments, alone (host only): throws
+void prefill_attn_check(int dtype, int B, int H, int P);
+
 // ------------------------------------------------------------------ token alignment (k_align.hip)
 // The workspace of an alignment: p [B][A][N_cap][M_cap] f32 (sequence, alignment head, text row, key),
 // stat [B][A][2][M_cap], m [B][N_cap][M_cap]; N [B] and M [B] (device) are each sequence's rows and

@@ -76,6 +76,9 @@ class WhisperInferenceParams:
     no_speech_thold: float = 0.0
     # report each window's no-speech probability (window_info()) without skipping
     no_speech_prob: bool = False
+    # SPT_BLOCK_PREFILL: a prompt prefix ([prev] + prompt tokens) of at least P_min positions runs as one
+    # block pass per sequence slice instead of ceil(P / 4) chunked passes (prefill_stats()); low bits differ
+    block_prefill: bool = False
     # benchmark / test hooks
     ignore_eot: bool = False
     forced_tokens: Optional[np.ndarray] = None  # [batch][n] teacher forcing
@@ -115,7 +118,8 @@ def _infer_params(p: Optional[WhisperInferenceParams], keep: list) -> L.InferPar
     ip.flags = (L.SPT_SUPPRESS_BLANK if p.suppress_blank else 0) | \
                (L.SPT_NO_TIMESTAMPS if p.no_timestamps else 0) | (L.SPT_IGNORE_EOT if p.ignore_eot else 0) | \
                (L.SPT_SUPPRESS_NST if p.suppress_non_speech_tokens else 0) | \
-               (L.SPT_NO_SPEECH_PROB if p.no_speech_prob else 0)
+               (L.SPT_NO_SPEECH_PROB if p.no_speech_prob else 0) | \
+               (L.SPT_BLOCK_PREFILL if p.block_prefill else 0)
     if not float(p.no_speech_thold) >= 0.0:  # negative or NaN: refused here as the library refuses it
         raise TranscriptionError(L.SPT_ERR_INVALID_ARG, "no_speech_thold must be >= 0 (0: off)")
     ip.no_speech_thold = float(p.no_speech_thold)
@@ -373,6 +377,14 @@ class WhisperEngine:
         f, b = C.c_int32(0), C.c_int32(0)
         self._check(self._lib.spt_get_xq_stats(self._ctx, C.byref(f), C.byref(b)))
         return {"fused_launches": f.value, "fallbacks": b.value}
+
+    def prefill_stats(self) -> dict:
+        """The last call's prefix prefill (spt_get_prefill_stats): block passes run (one per decode-group
+        slice), the prefix rows they carried, and chunked passes of at most 4 positions."""
+        self._need()
+        a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.spt_get_prefill_stats(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return {"block_passes": a.value, "block_rows": b.value, "chunk_passes": c.value}
 
     def debug_mel(self, samples, seek: int = 0) -> np.ndarray:
         """The normalised log-mel [n_mels][3000] the encoder takes for the window at frame `seek`
