@@ -97,6 +97,15 @@ typedef struct {
                                           nothing resident.  bf16 / f16 engines; SPT_DTYPE_F32:
                                           SPT_ERR_UNSUPPORTED at create.  weight_bytes is the smaller arena;
                                           export / import work between contexts of the same file and flag */
+#define SPT_MODEL_CROSS_KV_F8 4u       /* SPT_HAS_CROSS_KV_F8: the decoder's cross K/V cache is kept in fp8 e4m3
+                                          (OCP) with one f32 scale per 64-element key row, 0.531 of the 16-bit
+                                          cache, and the decode-step cross-attention reads it.
+                                          Results differ from the unflagged context's within the model's own
+                                          tolerances; a row's bits stay its own in any batch.
+                                          bf16 / f16 engines; SPT_DTYPE_F32: SPT_ERR_UNSUPPORTED at create.
+                                          On such a context spt_transcribe_aligned* return SPT_ERR_UNSUPPORTED,
+                                          SPT_BLOCK_PREFILL is ignored (the chunked passes run) and the fused
+                                          cross-Q launch is not taken.  Combines with SPT_MODEL_QUANT_RESIDENT */
 
 typedef struct {
     const char* language;        /* ISO-639-1 ("en", "zh", ...); NULL or "auto" = auto-detect
@@ -267,6 +276,18 @@ spt_status spt_get_xq_stats(const spt_ctx* ctx, int32_t* fused_launches, int32_t
  * may be NULL; a call that fails leaves zeros. */
 #define SPT_HAS_BLOCK_PREFILL 1
 spt_status spt_get_prefill_stats(const spt_ctx* ctx, int32_t* block_passes, int32_t* block_rows, int32_t* chunk_passes);
+
+/* The fp8 cross K/V cache (additive over ABI 14, announced by SPT_HAS_CROSS_KV_F8 and the word "crosskvf8"
+ * in spt_version()).  spt_get_cross_kv_info: format 0 = the engine dtype, 1 = e4m3 codes with
+ * a scale per key row; the bytes of the cache in the workspace (max_batch windows) and of the 16-bit staging
+ * buffer an fp8 cache is filled through (0 without the flag).  Any pointer may be NULL.
+ * spt_debug_cross_kv: layer `layer`, window `window` (of the last call's last encoded window batch) of the
+ * cache as f32, k and v [n_head][n_audio_ctx][64] each; an fp8 cache is dequantised on the device by the
+ * conversion its kernels use (f32(code) * scale).  SPT_ERR_INVALID_ARG before any window was encoded or
+ * for a layer / window out of range. */
+#define SPT_HAS_CROSS_KV_F8 1
+spt_status spt_get_cross_kv_info(const spt_ctx* ctx, int32_t* format, int64_t* cache_bytes, int64_t* staging_bytes);
+spt_status spt_debug_cross_kv(spt_ctx* ctx, int32_t layer, int32_t window, float* k, float* v);
 
 /* The no-speech probability and the silence skip (additive over ABI 14, announced by
  * SPT_HAS_NO_SPEECH and the word "nospeech" in spt_version()).  The probability of
@@ -440,6 +461,19 @@ spt_status spt_debug_attn_cross(int32_t device, int32_t dtype, int32_t mode, con
                                 const float* v, float pad_value, int32_t B, int32_t B_layout, int32_t b0, int32_t H,
                                 int32_t T_enc, int32_t Tq, int32_t splits, const int32_t* kvrow, int32_t share,
                                 float* out, float* part, char* err, size_t errlen);
+/* The fp8 cross K/V kernels alone (SPT_HAS_CROSS_KV_F8): spt_debug_attn_cross's arguments
+ * without splits (mode, q, k, v, pad_value, B, B_layout, b0, H, T_enc, Tq, kvrow, share, out, part as there;
+ * dtype bf16 or f16, SPT_DTYPE_F32: SPT_ERR_UNSUPPORTED).  k and v are rounded to dtype and quantised per key
+ * row; kq, vq [B_layout][H][T_enc][64] receive the dequantised rows and k_scale, v_scale [B_layout][H][T_enc]
+ * the scales.  The host quantiser fills the four before the device is looked for, so a valid call without a
+ * device returns them with SPT_ERR_DEVICE; on a device they are the device quantiser's, read back through
+ * the kernels' conversion, and one launch in the chosen mode gives out / part.  The keys that pad the last
+ * 32-key block carry the code of 1.0 in every element and pad_value as their scale (NaN included), so they
+ * dequantise to pad_value as spt_debug_attn_cross's do: no result may depend on them. */
+spt_status spt_debug_attn_cross_quant(int32_t device, int32_t dtype, int32_t mode, const float* q, const float* k,
+                                   const float* v, float pad_value, int32_t B, int32_t B_layout, int32_t b0, int32_t H,
+                                   int32_t T_enc, int32_t Tq, const int32_t* kvrow, int32_t share, float* kq, float* vq,
+                                   float* k_scale, float* v_scale, float* out, float* part, char* err, size_t errlen);
 /* The block prefill's attention kernels alone (SPT_HAS_BLOCK_PREFILL), under the
  * rules of the hooks above; every buffer a kernel writes starts with each byte 0xFF.
  * Self: qkv [B*P][3*H*64] (q | k | v, head h at h*64; rounded to dtype) are positions 0..P-1 of B

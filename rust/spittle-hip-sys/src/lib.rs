@@ -68,6 +68,8 @@ pub const SPT_BLOCK_PREFILL: u32 = 32;
 pub const SPT_MODEL_WEIGHTS_EXTERNAL: u32 = 1;
 /// quantised decoder matrices of a ggml file stay resident in their blocks (SPT_HAS_QUANT_RESIDENT)
 pub const SPT_MODEL_QUANT_RESIDENT: u32 = 2;
+/// the cross K/V cache in fp8 e4m3 with one f32 scale per key row (SPT_HAS_CROSS_KV_F8)
+pub const SPT_MODEL_CROSS_KV_F8: u32 = 4;
 
 /// the arguments of `spt_debug_gemv` (one decoder GEMV launch on caller-supplied arrays)
 #[repr(C)]
@@ -512,6 +514,35 @@ extern "C" {
     // block prefill of the prompt prefix (SPT_HAS_BLOCK_PREFILL, additive over ABI 14): the last call's
     // block passes, the prefix rows they carried, and its chunked prefill passes
     pub fn spt_get_prefill_stats(ctx: *const spt_ctx, block_passes: *mut i32, block_rows: *mut i32, chunk_passes: *mut i32) -> spt_status;
+    // the fp8 cross K/V cache (SPT_HAS_CROSS_KV_F8, additive over ABI 14): its format (0 engine dtype, 1 e4m3 +
+    // row scales) and bytes, one (layer, window) of it as f32, and its kernels alone
+    pub fn spt_get_cross_kv_info(ctx: *const spt_ctx, format: *mut i32, cache_bytes: *mut i64, staging_bytes: *mut i64) -> spt_status;
+    pub fn spt_debug_cross_kv(ctx: *mut spt_ctx, layer: i32, window: i32, k: *mut f32, v: *mut f32) -> spt_status;
+    pub fn spt_debug_attn_cross_quant(
+        device: i32,
+        dtype: i32,
+        mode: i32,
+        q: *const f32,
+        k: *const f32,
+        v: *const f32,
+        pad_value: f32,
+        b: i32,
+        b_layout: i32,
+        b0: i32,
+        h: i32,
+        t_enc: i32,
+        tq: i32,
+        kvrow: *const i32,
+        share: i32,
+        kq: *mut f32,
+        vq: *mut f32,
+        k_scale: *mut f32,
+        v_scale: *mut f32,
+        out: *mut f32,
+        part: *mut f32,
+        err: *mut c_char,
+        errlen: usize,
+    ) -> spt_status;
     // the block prefill's attention kernels alone (cache: in and out)
     pub fn spt_debug_attn_prefill_self(
         device: i32,
@@ -1228,6 +1259,8 @@ pub const SPT_HAS_TOKEN_TIMESTAMPS: c_int = 1;
 pub const SPT_HAS_NO_SPEECH: c_int = 1;
 /// `SPT_BLOCK_PREFILL`, `spt_get_prefill_stats` and the prefill attention hooks are present
 pub const SPT_HAS_BLOCK_PREFILL: c_int = 1;
+/// `SPT_MODEL_CROSS_KV_F8`, `spt_get_cross_kv_info`, `spt_debug_cross_kv` and the fp8 attention hook are present
+pub const SPT_HAS_CROSS_KV_F8: c_int = 1;
 
 /// a text token's start and end (10 ms units), probability and index into `spt_result.tokens`
 #[repr(C)]

@@ -211,6 +211,17 @@ pub struct PrefillStats {
     pub chunk_passes: i32,
 }
 
+/// The cross K/V cache of a loaded model (`spt_get_cross_kv_info`, `SPT_HAS_CROSS_KV_F8`).
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct CrossKvInfo {
+    /// e4m3 codes with a scale per key row (`load_model_cross_kv_f8`), else the engine dtype
+    pub fp8: bool,
+    /// bytes of the cache in the workspace
+    pub cache_bytes: i64,
+    /// bytes of the 16-bit staging buffer an fp8 cache is filled through (0 otherwise)
+    pub staging_bytes: i64,
+}
+
 /// One window of the last call (`spt_get_window_info`, `SPT_HAS_NO_SPEECH`).
 #[derive(Debug, Clone, PartialEq)]
 pub struct WindowInfo {
@@ -367,6 +378,34 @@ impl HipWhisperEngine {
         }
         mp.flags |= sys::SPT_MODEL_QUANT_RESIDENT;
         self.load_model_raw(model_path, mp)
+    }
+
+    /// Load option `SPT_MODEL_CROSS_KV_F8`: the decoder's cross K/V cache is kept in fp8 e4m3 with one f32
+    /// scale per key row, 0.531 of the 16-bit cache.  Results differ from the unflagged model's within
+    /// the model's own tolerances; `transcribe_aligned*` is refused, `set_block_prefill` is ignored.
+    /// `f16`: the fp16 engine, else bf16; `quant_resident` adds `SPT_MODEL_QUANT_RESIDENT`.
+    pub fn load_model_cross_kv_f8(&mut self, model_path: &Path, params: HipModelParams, f16: bool, quant_resident: bool) -> Result<(), Box<dyn Error>> {
+        let mut mp = model_params_f16(&params);
+        if !f16 {
+            mp.dtype = sys::SPT_DTYPE_BF16;
+        }
+        mp.flags |= sys::SPT_MODEL_CROSS_KV_F8;
+        if quant_resident {
+            mp.flags |= sys::SPT_MODEL_QUANT_RESIDENT;
+        }
+        self.load_model_raw(model_path, mp)
+    }
+
+    /// The loaded model's cross K/V cache: its format and bytes.
+    pub fn cross_kv_info(&self) -> Result<CrossKvInfo, Box<dyn Error>> {
+        self.need()?;
+        let (mut f, mut c, mut s) = (0i32, 0i64, 0i64);
+        // SAFETY: a live context and three valid out-pointers
+        let st = unsafe { sys::spt_get_cross_kv_info(self.ctx, &mut f, &mut c, &mut s) };
+        if st != sys::SPT_OK {
+            return Err(status_error("cross K/V info", st, self.last_error()));
+        }
+        Ok(CrossKvInfo { fp8: f == 1, cache_bytes: c, staging_bytes: s })
     }
 
     /// What `load_model_quant_resident` kept: (weights held quantised, their bytes in the arena, their

@@ -82,6 +82,8 @@ EXPORTS = [
     "spt_get_window_info", "spt_debug_no_speech",
     # block prefill of the prompt prefix (SPT_HAS_BLOCK_PREFILL)
     "spt_get_prefill_stats", "spt_debug_attn_prefill_self", "spt_debug_attn_prefill_cross",
+    # the fp8 cross K/V cache (SPT_HAS_CROSS_KV_F8)
+    "spt_get_cross_kv_info", "spt_debug_cross_kv", "spt_debug_attn_cross_quant",
 ]
 
 
@@ -99,6 +101,8 @@ class Alignment(C.Structure):
                 ("n_words", C.c_int32)]
 
 SPT_MODEL_QUANT_RESIDENT = 2
+SPT_MODEL_CROSS_KV_F8 = 4  # SPT_HAS_CROSS_KV_F8: the cross K/V cache in fp8 e4m3 with a scale per key row
+SPT_HAS_CROSS_KV_F8 = 1
 SPT_GGML_Q4_1, SPT_GGML_Q5_0, SPT_GGML_Q5_1 = 3, 6, 7
 SPT_GV_BIAS, SPT_GV_BIAS_GELU, SPT_GV_PARTIAL, SPT_GV_QKV_CACHE, SPT_GV_LOGITS, SPT_GV_BIAS_RESID = range(6)
 SPT_QGEMV_A_DIRECT, SPT_QGEMV_A_LN = 0, 1
@@ -377,6 +381,9 @@ def load():
     L.spt_get_xq_stats.argtypes = [vp, ip, ip]
     L.spt_get_prefill_stats.argtypes = [vp, ip, ip, ip]
     L.spt_get_prefill_stats.restype = C.c_int
+    L.spt_get_cross_kv_info.argtypes = [vp, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.spt_debug_cross_kv.argtypes = [vp, C.c_int32, C.c_int32, fp, fp]
+    L.spt_get_cross_kv_info.restype = L.spt_debug_cross_kv.restype = C.c_int
     L.spt_get_window_info.argtypes = [vp, C.POINTER(WindowInfo), C.c_int32, ip]
     L.spt_get_window_info.restype = C.c_int
     L.spt_debug_mel.argtypes = [vp, fp, C.c_size_t, fp]
@@ -546,8 +553,10 @@ def load():
     L.spt_debug_attn_prefill_self.argtypes = [i32, i32, fp, fp, i32, i32, i32, i32, fp, C.c_char_p, C.c_size_t]
     L.spt_debug_attn_prefill_cross.argtypes = [i32, i32, fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32p,
                                                i32, fp, C.c_char_p, C.c_size_t]
+    L.spt_debug_attn_cross_quant.argtypes = [i32, i32, i32, fp, fp, fp, C.c_float, i32, i32, i32, i32, i32, i32, i32p, i32,
+                                          fp, fp, fp, fp, fp, fp, C.c_char_p, C.c_size_t]
     for fn in ("spt_debug_attn_enc", "spt_debug_attn_self", "spt_debug_attn_cross", "spt_debug_xq_fused",
-               "spt_debug_attn_prefill_self", "spt_debug_attn_prefill_cross"):
+               "spt_debug_attn_prefill_self", "spt_debug_attn_prefill_cross", "spt_debug_attn_cross_quant"):
         getattr(L, fn).restype = C.c_int
     # the GEMM tiles and LayerNorm kernels alone
     i64 = C.c_int64

@@ -445,7 +445,7 @@ spt_status run_windows(spt_ctx* c, std::vector<Window>& win, const float* const*
 
 extern "C" {
 
-const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice, qresident, nospeech, blockprefill)"; }
+const char* spt_version(void) { return "spittle_amd 0.14.0 (gfx950, ABI 14: additive over ABI 12; moonshine, sensevoice, qresident, nospeech, blockprefill, crosskvf8)"; }
 
 const char* spt_language_code(int32_t lang_id) { return spt::lang_code(lang_id); }
 
@@ -487,12 +487,16 @@ spt_status spt_ctx_create(const char* model_spec, const spt_model_params* params
         set_err(err, errlen, "bad dtype");
         return SPT_ERR_INVALID_ARG;
     }
-    if (mp.flags & ~(SPT_MODEL_WEIGHTS_EXTERNAL | SPT_MODEL_QUANT_RESIDENT)) {
+    if (mp.flags & ~(SPT_MODEL_WEIGHTS_EXTERNAL | SPT_MODEL_QUANT_RESIDENT | SPT_MODEL_CROSS_KV_F8)) {
         set_err(err, errlen, "unknown spt_model_params.flags bits");
         return SPT_ERR_INVALID_ARG;
     }
     if ((mp.flags & SPT_MODEL_QUANT_RESIDENT) && mp.dtype == SPT_DTYPE_F32) {
         set_err(err, errlen, "SPT_MODEL_QUANT_RESIDENT needs a bf16 or f16 engine (the f32 engine keeps no quantised matrices)");
+        return SPT_ERR_UNSUPPORTED;
+    }
+    if ((mp.flags & SPT_MODEL_CROSS_KV_F8) && mp.dtype == SPT_DTYPE_F32) {
+        set_err(err, errlen, "SPT_MODEL_CROSS_KV_F8 needs a bf16 or f16 engine (the f32 engine keeps its cross K/V in f32)");
         return SPT_ERR_UNSUPPORTED;
     }
     spt::ModelDims dm;
@@ -532,7 +536,7 @@ spt_status spt_ctx_create(const char* model_spec, const spt_model_params* params
     try {
         c->eng.reset(new Engine(dm, mp.dtype == SPT_DTYPE_BF16 ? spt::DT_BF16 : mp.dtype == SPT_DTYPE_F16 ? spt::DT_F16 : spt::DT_F32, mp.device,
                                 mp.max_batch, seed, file.get(), (mp.flags & SPT_MODEL_WEIGHTS_EXTERNAL) != 0,
-                                (mp.flags & SPT_MODEL_QUANT_RESIDENT) != 0));
+                                (mp.flags & SPT_MODEL_QUANT_RESIDENT) != 0, (mp.flags & SPT_MODEL_CROSS_KV_F8) != 0));
         if (file) c->vocab.reset(new spt::Vocab(file->vocab(), dm.n_vocab, spt::specials_for(dm.n_vocab)));
     } catch (const std::exception& e) {
         set_err(err, errlen, e.what());
@@ -776,6 +780,28 @@ spt_status spt_get_xq_stats(const spt_ctx* ctx, int32_t* fused_launches, int32_t
     return SPT_OK;
 }
 
+spt_status spt_get_cross_kv_info(const spt_ctx* ctx, int32_t* format, int64_t* cache_bytes, int64_t* staging_bytes) {
+    if (!ctx) return SPT_ERR_INVALID_ARG;
+    int f = 0;
+    int64_t c = 0, s = 0;
+    ctx->eng->cross_kv_info(&f, &c, &s);
+    if (format) *format = f;
+    if (cache_bytes) *cache_bytes = c;
+    if (staging_bytes) *staging_bytes = s;
+    return SPT_OK;
+}
+
+spt_status spt_debug_cross_kv(spt_ctx* ctx, int32_t layer, int32_t window, float* k, float* v) {
+    if (!ctx || !k || !v) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
+    try {
+        if (!ctx->eng->debug_cross_kv(layer, window, k, v))
+            return fail(ctx, SPT_ERR_INVALID_ARG, "no window has been encoded on this context");
+        return SPT_OK;
+    } catch (const std::exception& e) {
+        return fail(ctx, classify(e), e.what());
+    }
+}
+
 spt_status spt_get_prefill_stats(const spt_ctx* ctx, int32_t* block_passes, int32_t* block_rows, int32_t* chunk_passes) {
     if (!ctx) return SPT_ERR_INVALID_ARG;
     const spt::CallStats& c = ctx->eng->call_stats();
@@ -899,6 +925,10 @@ static spt_status transcribe_aligned_batch_impl(spt_ctx* ctx, const float* const
                                                size_t batch, const spt_infer_params* params, spt_result** out,
                                                spt_alignment** align) {
     if (!ctx || !out || !align || (batch && (!pcm || !n_samples))) return fail(ctx, SPT_ERR_INVALID_ARG, "null argument");
+    if (ctx->eng->cross_kv_f8()) {  // align_qk reads 16-bit K rows
+        for (size_t u = 0; u < batch; ++u) out[u] = nullptr, align[u] = nullptr;
+        return fail(ctx, SPT_ERR_UNSUPPORTED, "token alignment is not available on an SPT_MODEL_CROSS_KV_F8 context (its cross K is fp8)");
+    }
     spt_infer_params dflt;
     spt_default_infer_params(&dflt);
     if (!params) params = &dflt;

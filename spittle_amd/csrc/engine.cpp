@@ -10,6 +10,7 @@
 #include "engine.h"
 #include "ggml_file.h"
 #include "ggml_qpack.h"
+#include "kv_f8.h"
 #include "prefill_host.h"
 
 #include <cstdio>
@@ -88,8 +89,11 @@ struct Carver {
 void Engine::select() const { HIP_CHECK(hipSetDevice(dev_)); }
 
 Engine::Engine(const ModelDims& dm, int dtype, int device, int max_batch, uint64_t seed, const GgmlFile* src,
-               bool external_weights, bool quant_resident)
+               bool external_weights, bool quant_resident, bool cross_kv_f8)
     : dm_(dm), dt_(dtype), dev_(device), max_batch_(max_batch), seed_(seed) {
+    if (cross_kv_f8 && dtype == DT_F32)
+        throw std::runtime_error("SPT_MODEL_CROSS_KV_F8 needs a bf16 or f16 engine");
+    kv_f8_ = cross_kv_f8;
     if (quant_resident && dtype == DT_F32)
         throw std::runtime_error("SPT_MODEL_QUANT_RESIDENT needs a bf16 or f16 engine");
     if (dm_.d % 128 || dm_.d / 64 != dm_.n_head) throw std::runtime_error("unsupported model width");
@@ -661,7 +665,16 @@ void Engine::alloc_workspace() {
         ao_ = A(B * T * d);
         ff_ = A(B * T * 4 * d);
         enc_out_ = A(B * T * d);
-        ckv_ = A(L * kv_layer_elems((int)B, dm_.n_head, (int)T));
+        if (kv_f8_) {  // fp8 records, and the 16-bit layers they are quantised from
+            kvs_layers_ = std::max(1, cdiv((int)L, 8));
+            ckv_bytes_ = L * f8::layer_bytes((int)B, dm_.n_head, (int)T);
+            kvs_bytes_ = kvs_layers_ * kv_layer_elems((int)B, dm_.n_head, (int)T) * esz_;
+            ckv_ = c.take(ckv_bytes_);
+            kvs_ = c.take(kvs_bytes_);
+        } else {
+            ckv_bytes_ = L * kv_layer_elems((int)B, dm_.n_head, (int)T) * esz_;
+            ckv_ = A(L * kv_layer_elems((int)B, dm_.n_head, (int)T));
+        }
         suppress_ = (uint32_t*)c.take((V / 32 + 1) * 4);
         suppress_lang_ = (uint32_t*)c.take((V / 32 + 1) * 4);
         scratch_ = (double*)c.take(64);
@@ -985,7 +998,71 @@ void Engine::run_cross_kv(int B) {
     GemmArgs g{};
     g.A = enc_out_; g.lda = d; g.W = ckv_w_; g.ldw = d; g.M = B * T; g.N = dm_.n_dec * 2 * d; g.K = d;
     g.bias = ckv_b_; g.C = ckv_; g.kv_B = B; g.kv_T = T; g.kv_H = dm_.n_head;
-    gemm_nt(dt_, EPI_KVSPLIT, g, 1, st_);
+    if (!kv_f8_) {
+        gemm_nt(dt_, EPI_KVSPLIT, g, 1, st_);
+        return;
+    }
+    // SPT_MODEL_CROSS_KV_F8: the same product a group of layers at a time (rows [2 l0 d, 2 (l0 + nl) d) of the
+    // weights) into the 16-bit staging layers, on the tile the single GEMM would take -- every staged element
+    // is the bit the 16-bit cache would hold -- then quantised into the records of those layers
+    const int tile = gemm_nt_plan(dt_, EPI_KVSPLIT, g, 1, 0);
+    for (int l0 = 0; l0 < dm_.n_dec; l0 += kvs_layers_) {
+        const int nl = std::min(kvs_layers_, dm_.n_dec - l0);
+        GemmArgs s = g;
+        s.W = (const char*)ckv_w_ + (int64_t)2 * l0 * d * d * esz_;
+        s.bias = ckv_b_ + (int64_t)2 * l0 * d;
+        s.N = nl * 2 * d;
+        s.C = kvs_;
+        gemm_nt_variant(dt_, EPI_KVSPLIT, s, 1, tile, st_);
+        kv_quant_f8(dt_, kvs_, (char*)ckv_ + l0 * f8::layer_bytes(B, dm_.n_head, T), nl, B, dm_.n_head, T, st_);
+    }
+}
+
+int64_t Engine::ckv_layer_bytes(int E) const {
+    return kv_f8_ ? f8::layer_bytes(E, dm_.n_head, dm_.n_audio_ctx) : kv_layer_elems(E, dm_.n_head, dm_.n_audio_ctx) * esz_;
+}
+int64_t Engine::ckv_window_bytes() const {
+    return kv_f8_ ? (int64_t)dm_.n_head * f8::kRecBytes : (int64_t)dm_.n_head * 4096 * esz_;
+}
+
+bool Engine::debug_cross_kv(int layer, int window, float* k, float* v) {
+    select();
+    const int E = enc_E_, H = dm_.n_head, T = dm_.n_audio_ctx;
+    if (E < 1) return false;
+    if (layer < 0 || layer >= dm_.n_dec || window < 0 || window >= E) throw std::runtime_error("debug_cross_kv: layer or window out of range");
+    HIP_CHECK(hipStreamSynchronize(st_));
+    const int64_t n = (int64_t)H * T * 64;
+    float* tmp = nullptr;
+    HIP_CHECK(hipMalloc(&tmp, (size_t)(2 * n) * 4));
+    try {
+        const char* lay = (const char*)ckv_ + ckv_layer_bytes(E) * layer;
+        if (kv_f8_) {
+            kv_dequant_f8(lay, E, H, T, window, 1, tmp, tmp + n, nullptr, nullptr, st_);
+            HIP_CHECK(hipMemcpyAsync(k, tmp, (size_t)n * 4, hipMemcpyDeviceToHost, st_));
+            HIP_CHECK(hipMemcpyAsync(v, tmp + n, (size_t)n * 4, hipMemcpyDeviceToHost, st_));
+            HIP_CHECK(hipStreamSynchronize(st_));
+        } else {
+            // the layer's blocks as f32, gathered on the host
+            const int64_t ne = kv_layer_elems(E, H, T);
+            HIP_CHECK(hipFree(tmp));
+            tmp = nullptr;
+            HIP_CHECK(hipMalloc(&tmp, (size_t)ne * 4));
+            to_f32(dt_, lay, tmp, ne, st_);
+            std::vector<float> h((size_t)ne);
+            HIP_CHECK(hipMemcpyAsync(h.data(), tmp, (size_t)ne * 4, hipMemcpyDeviceToHost, st_));
+            HIP_CHECK(hipStreamSynchronize(st_));
+            for (int kvi = 0; kvi < 2; ++kvi)
+                for (int hh = 0; hh < H; ++hh)
+                    for (int t = 0; t < T; ++t)
+                        memcpy((kvi ? v : k) + ((int64_t)hh * T + t) * 64,
+                               h.data() + kv_offset(0, kvi, window, hh, t, 0, E, H, T), 64 * sizeof(float));
+        }
+    } catch (...) {
+        if (tmp) (void)hipFree(tmp);
+        throw;
+    }
+    HIP_CHECK(hipFree(tmp));
+    return true;
 }
 
 // One decoder pass: 8 launches per layer.  The residual stream is f32 rows; fc2 splits K over
@@ -1006,6 +1083,7 @@ void Engine::enqueue_decoder_pass(DecGroup& g, int E, int Tq, const DecodeReques
 float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
     const int d = dm_.d, H = dm_.n_head, ctx = dm_.n_text_ctx, T = dm_.n_audio_ctx, B = g.B, R = B * Tq;
     const int64_t self_layer = (int64_t)2 * B * H * ctx * 64, cross_layer = kv_layer_elems(E, H, T);
+    if (kv_f8_ && tap_) throw std::runtime_error("token alignment reads 16-bit cross K: not on an SPT_MODEL_CROSS_KV_F8 context");
     // window map: rows j * share .. + share - 1 attend to window g.kvrow[j * share]; without one,
     // row b attends to window g.b0 + b (the cross-attention key split applies there only)
     const bool mapped = g.share > 0;
@@ -1025,12 +1103,13 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
     // than a launch), by a merge kernel for more (the prologue repeats the merge in each of its
     // 80 workgroups: 15 us at a beam's 5 rows)
     const bool vw_merge = vw && R > 1;
-    const int xs = vw ? (vw_merge ? 1 : 8) : mapped ? 1 : xsplit_;
+    // (an fp8 cross K/V cache takes no key chunks: DESIGN 4.8)
+    const int xs = vw ? (vw_merge ? 1 : 8) : (mapped || kv_f8_) ? 1 : xsplit_;
     const int ks = esz_ == 2 ? 128 : 64;
     hipStream_t st = g.st;
     // LN2 + cross-Q and the cross-attention in one launch: one-token passes on the unsplit
     // 8-wave path with identity windows whose workgroups are all resident at once; bitwise the two launches
-    const bool fuse = xq_on_ && probe_kind_ < 0 && Tq == 1 && !vw && !mapped && xs == 1 && dm_.n_dec <= 64 &&
+    const bool fuse = xq_on_ && !kv_f8_ && probe_kind_ < 0 && Tq == 1 && !vw && !mapped && xs == 1 && dm_.n_dec <= 64 &&
                       dec_xq_fused_ok(dt_, B, d, H, T, n_cu_);
     xq_enq_ = fuse ? dm_.n_dec : 0;
     if (fuse) {
@@ -1066,7 +1145,8 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
         void* skv_l = (char*)g.skv + self_layer * l * esz_;
         // layer l of the cross K/V (kv_offset layout, E windows), at this group's first window when
         // the rows map to windows one to one
-        const void* ckv_l = (const char*)ckv_ + (cross_layer * l + (mapped ? 0 : (int64_t)g.b0 * H * 4096)) * esz_;
+        const void* ckv_l = kv_f8_ ? (const char*)ckv_ + ckv_layer_bytes(E) * l + (mapped ? 0 : g.b0 * ckv_window_bytes())
+                                   : (const char*)ckv_ + (cross_layer * l + (mapped ? 0 : (int64_t)g.b0 * H * 4096)) * esz_;
         // LN1 + QKV projection + self K/V append, then the self-attention
         {
             GemvArgs a{};
@@ -1110,6 +1190,14 @@ float* Engine::enqueue_layers(DecGroup& g, int E, int Tq) {
         }
         pmark(0, l, 0);
         if (fuse) {  // the attention ran in the cross-Q launch
+        } else if (kv_f8_) {  // the same two shapes over the fp8 records (k_dec_f8.hip)
+            if (vw) {
+                dec_cross_attn_vw_f8(dt_, g.dq, ckv_l, B, E, H, T, Tq, g.xpart, st, mapped ? g.kvrow : nullptr,
+                                     mapped ? g.share : 1, per_query);
+                if (vw_merge) dec_attn_part_merge(dt_, g.xpart, R, H, g.dao, st);
+            } else {
+                dec_cross_attn_f8(dt_, g.dq, ckv_l, B, E, H, T, Tq, g.dao, st, mapped ? g.kvrow : nullptr, mapped ? g.share : 1);
+            }
         } else if (vw) {
             dec_cross_attn_vw(dt_, g.dq, ckv_l, B, E, H, T, Tq, g.xpart, st, mapped ? g.kvrow : nullptr,
                               mapped ? g.share : 1, per_query);
@@ -1471,7 +1559,7 @@ void Engine::run_decode(int B, const DecodeRequest& rq, int* tokens, float* top1
         // sequence through the decoder layers only (no logits), positions 0..P-1
         const bool rows = !rq.row_prefix.empty();
         const int P = rows ? (int)rq.row_prefix[0].size() : (int)rq.prefix.size();
-        if (prefill_takes_block(rq.block_prefill, quant_flag_, P, pf_min_)) {
+        if (!kv_f8_ && prefill_takes_block(rq.block_prefill, quant_flag_, P, pf_min_)) {
             // SPT_BLOCK_PREFILL: the whole prefix in one pass per slice of the group's sequences
             int* h = g.host_tok.data() + g.host_used;
             for (int b = 0; b < g.B; ++b)
@@ -2079,10 +2167,14 @@ double Engine::probe(int kind, int iters, double* work, int* is_flops) {
         case 0:  // cross-attention of layers 0..nl-1 (one launch each) over this group's cross K/V
             launch = [&] {
                 for (int l = 0; l < nl; ++l)
-                    dec_cross_attn(dt_, g.dq, (const char*)ckv_ + kv_layer_elems(B, H, T) * l * esz_, std::min(Bg, B), B,
-                                   H, T, 1, g.dao, st_, xsplit_, g.xpart);
+                    if (kv_f8_)
+                        dec_cross_attn_f8(dt_, g.dq, (const char*)ckv_ + ckv_layer_bytes(B) * l, std::min(Bg, B), B, H, T, 1,
+                                          g.dao, st_);
+                    else
+                        dec_cross_attn(dt_, g.dq, (const char*)ckv_ + kv_layer_elems(B, H, T) * l * esz_, std::min(Bg, B), B,
+                                       H, T, 1, g.dao, st_, xsplit_, g.xpart);
             };
-            *work = 2.0 * std::min(Bg, B) * H * T * 64 * esz_;
+            *work = kv_f8_ ? (double)std::min(Bg, B) * H * cdiv(T, 32) * f8::kRecBytes : 2.0 * std::min(Bg, B) * H * T * 64 * esz_;
             break;
         case 1:
             launch = [&] { dec_self_attn(dt_, g.dq, g.skv, Bg, H, ctx, 1, g.ds, g.dao, st_); };

@@ -88,10 +88,12 @@ public:
     // (dm from ggml_dims(*src)); the file is read during construction only
     // external_weights: allocate the weight arena but leave it unfilled; import_weights() (e.g.
     // the bytes of rank 0's arena after an RCCL broadcast) makes the engine usable
+    // cross_kv_f8 (SPT_MODEL_CROSS_KV_F8; bf16 / f16 engines): the cross K/V cache holds fp8 e4m3 records with
+    // one f32 scale per key row (kv_f8.h), filled through a 16-bit staging buffer of a few layers
     // quant_resident (SPT_MODEL_QUANT_RESIDENT; bf16 / f16 engines, ggml files): the decoder's matrices and the
     // token embedding whose file type has a packed layout (ggml_qpack.h) stay quantised in the arena
     Engine(const ModelDims& dm, int dtype, int device, int max_batch, uint64_t seed, const GgmlFile* src = nullptr,
-           bool external_weights = false, bool quant_resident = false);
+           bool external_weights = false, bool quant_resident = false, bool cross_kv_f8 = false);
     ~Engine();
     Engine(const Engine&) = delete;
     Engine& operator=(const Engine&) = delete;
@@ -118,6 +120,15 @@ public:
     void commit_weights();
     // the workspace arena plus the block prefill workspaces allocated so far
     int64_t workspace_bytes() const { return abytes_ + pf_bytes_; }
+    // the cross K/V cache (spt_get_cross_kv_info): 0 = engine dtype, 1 = e4m3 records; its bytes in the
+    // workspace at max_batch windows, and those of the 16-bit staging buffer the fp8 cache is filled through
+    bool cross_kv_f8() const { return kv_f8_; }
+    void cross_kv_info(int* format, int64_t* cache_bytes, int64_t* staging_bytes) const {
+        *format = kv_f8_ ? 1 : 0; *cache_bytes = ckv_bytes_; *staging_bytes = kvs_bytes_;
+    }
+    // one (layer, window) of the last encode_windows' cross K/V as f32 [H][T_enc][64] each (host), an fp8
+    // cache dequantised on the device by the kernels' conversion; false before any window was encoded
+    bool debug_cross_kv(int layer, int window, float* k, float* v);
     const Timings& timings() const { return tm_; }
     const CallStats& call_stats() const { return cs_; }
     void reset_call_stats() { cs_ = CallStats(); }
@@ -387,6 +398,15 @@ private:
     float* x_ = nullptr;
     void *xn_ = nullptr, *qkv_ = nullptr, *ao_ = nullptr, *ff_ = nullptr, *enc_out_ = nullptr;
     void* ckv_ = nullptr;   // cross K/V, per layer [47][B][H][2][32][64] (kernels.h kv_offset)
+    // SPT_MODEL_CROSS_KV_F8: ckv_ holds fp8 records instead (kv_f8.h: per layer [47][B][H] x 4352 bytes), filled
+    // by kv_quant_f8 from kvs_, kvs_layers_ layers of the 16-bit layout that the K/V GEMM writes group by group
+    bool kv_f8_ = false;
+    void* kvs_ = nullptr;
+    int kvs_layers_ = 0;
+    int64_t ckv_bytes_ = 0, kvs_bytes_ = 0;
+    // bytes of one layer of the cross K/V of E windows, and of a window's step inside a layer
+    int64_t ckv_layer_bytes(int E) const;
+    int64_t ckv_window_bytes() const;
     uint32_t* suppress_ = nullptr;
     uint32_t* suppress_lang_ = nullptr;  // all but the language tokens (language detection)
     bool suppress_lang_ready_ = false;

@@ -253,6 +253,23 @@ void dec_xq_fused_prepare(int dtype);
 // kernel's output), for a plain (A_DIRECT) cross output projection
 void dec_attn_part_merge(int dtype, const float* part, int R, int H, void* out, hipStream_t st);
 
+// ------------------------------------------------------------------ fp8 cross K/V (k_dec_f8.hip; format: kv_f8.h)
+// staged: `layers` layers of B windows in the kv_offset layout (bf16 / f16) -> recs: their records, layer
+// after layer.  The rows that pad the last 32-key block get code 0 and scale 1.
+void kv_quant_f8(int dtype, const void* staged, void* recs, int layers, int B, int H, int T_enc, hipStream_t st);
+// recs: one layer's records of B_layout windows -> k, v [nb][H][T_enc][64] f32 = f32(code) * scale of
+// windows b0 .. b0 + nb - 1, and their scales [nb][H][T_enc] (optional), by the kernels' conversion
+void kv_dequant_f8(const void* recs, int B_layout, int H, int T_enc, int b0, int nb, float* k, float* v, float* k_scale,
+                   float* v_scale, hipStream_t st);
+// dec_cross_attn / dec_cross_attn_vw over one layer's records (kv: advanced to the first of the B
+// windows, + b0 * H * 4352 bytes, or at the layer with a window map); dtype (bf16 / f16) is q's and
+// out's.  No key chunks.  The partials are dec_cross_attn_vw's, merged by dec_attn_part_merge / A_ATTN;
+// the 8-wave output, vw + merge and vw + per_query + merge are bitwise equal.
+void dec_cross_attn_f8(int dtype, const void* q, const void* kv, int B, int B_layout, int H, int T_enc, int Tq, void* out,
+                       hipStream_t st, const int* kvrow = nullptr, int share = 1);
+void dec_cross_attn_vw_f8(int dtype, const void* q, const void* kv, int B, int B_layout, int H, int T_enc, int Tq,
+                          float* part, hipStream_t st, const int* kvrow = nullptr, int share = 1, bool per_query = false);
+
 struct FinalizeArgs {
     const void* part; int n_tiles;        // logits top-2 partials [B][n_tiles]
     int eot; int ignore_eot; int n_vocab;

@@ -47,6 +47,10 @@ class WhisperModelParams:
     # quantised in HBM and are dequantised in the decoder GEMVs (bf16 / f16 engines; results bit for bit
     # those without it).  Opt-in: it shrinks the weight arena; the decode pass is not faster
     quant_resident: bool = False
+    # SPT_MODEL_CROSS_KV_F8: the cross K/V cache in fp8 e4m3 with one f32 scale per key row (bf16 / f16 engines):
+    # 0.531 of the 16-bit cache.  Opt-in: results change within the tolerances of DESIGN 7; aligned calls are
+    # refused, block_prefill is ignored and the fused cross-Q launch is not taken
+    cross_kv_f8: bool = False
 
 
 @dataclass
@@ -197,7 +201,8 @@ class WhisperEngine:
         mp.max_batch = int(self.params.max_batch)
         mp.seed = int(self.params.seed)
         mp.flags = (L.SPT_MODEL_WEIGHTS_EXTERNAL if self.params.external_weights else 0) | \
-                   (L.SPT_MODEL_QUANT_RESIDENT if self.params.quant_resident else 0)
+                   (L.SPT_MODEL_QUANT_RESIDENT if self.params.quant_resident else 0) | \
+                   (L.SPT_MODEL_CROSS_KV_F8 if self.params.cross_kv_f8 else 0)
         ctx = C.c_void_p()
         err = C.create_string_buffer(1024)
         st = self._lib.spt_ctx_create(str(model_path).encode(), C.byref(mp), C.byref(ctx), err, 1024)
@@ -377,6 +382,15 @@ class WhisperEngine:
         f, b = C.c_int32(0), C.c_int32(0)
         self._check(self._lib.spt_get_xq_stats(self._ctx, C.byref(f), C.byref(b)))
         return {"fused_launches": f.value, "fallbacks": b.value}
+
+    def cross_kv_info(self) -> dict:
+        """The cross K/V cache (spt_get_cross_kv_info): format 0 = the engine dtype, 1 = e4m3 codes with a scale
+        per key row; its bytes in the workspace, and those of the 16-bit staging buffer an fp8 cache is filled
+        through (0 without cross_kv_f8)."""
+        self._need()
+        f, c, s = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.spt_get_cross_kv_info(self._ctx, C.byref(f), C.byref(c), C.byref(s)))
+        return {"format": f.value, "cache_bytes": c.value, "staging_bytes": s.value}
 
     def prefill_stats(self) -> dict:
         """The last call's prefix prefill (spt_get_prefill_stats): block passes run (one per decode-group
